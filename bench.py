@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- OTVM per-frame inference throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A step = one frame of the hot path (EvalModel.forward: trimap propagation + alpha prediction + memorize)
 on a synthetic 1920x1080 clip (BASELINE.json configs[2]: T=100, memory every 5 frames, max 5 slots).
@@ -13,10 +13,11 @@ the timed region starts.  One process per GPU; with N>1 every rank mattes its ow
 are independent, frames inside a sequence are strictly sequential -- SURVEY.md 8e), no data-path
 collective; ranks meet in one all-reduce for the timing/metric sums.  value = total frames / max time.
 
-Extra legs (rank 0, N=1): `roofline` (all convolution launches of the plan: algorithmic FLOPs / HIP-event
-time per launch, instrumented replay of the timed frames on the same stream; `traffic` = HBM-side bytes per
-launch from two short child runs of this script under `rocprofv3 --pmc`, live_traffic) and `cpu_baseline`
-(the CPU oracle timed on the host cores for one steady-state frame of the same clip).
+A plain run sets up, runs the lead-in and warm-up, times the steps, writes the outputs of the last timed step (--dump-outputs)
+and prints the result line.  Extra legs, only with --full (rank 0, N=1): `roofline` (all convolution launches of the plan:
+algorithmic FLOPs / HIP-event time per launch, instrumented replay of the timed frames on the same stream; `traffic` = HBM-side
+bytes per launch from two short child runs of this script under `rocprofv3 --pmc`, live_traffic), `cpu_baseline` (the CPU oracle
+timed on the host cores for one steady-state frame of the same clip) and, with --precision f16, `alpha_error_vs_f16x3`.
 """
 import argparse
 import json
@@ -183,6 +184,45 @@ def frame_kwargs(t, T, skip, max_num, stress_bank=False):
                 max_memory_num=max_num)
 
 
+OUTPUT_NAMES = ("scaled_imgs", "preds_trimap", "tri_gt", "preds_alpha", "scaled_gts")   # EvalModel.forward's 5-tuple
+DUMP_BUDGET = 64 * 10 ** 6 - (1 << 16)  # bytes of the arrays of --dump-outputs together (64 MB, room left for the .npy headers)
+DUMP_SAMPLE = 1 << 20                   # values kept of an output written as a sample
+
+
+def dump_plan(shapes, budget=DUMP_BUDGET, sample=DUMP_SAMPLE):
+    """[(name, whole)] for the (name, shape) pairs, in order: an output is written whole (float32) when it fits the budget with a
+    sample's room left for every output after it, otherwise as `sample` values at fixed positions (dump_outputs)."""
+    plan, used = [], 0
+    for i, (name, shape) in enumerate(shapes):
+        n = int(np.prod(shape))
+        rest = sum(min(int(np.prod(s)), sample) for _, s in shapes[i + 1:]) * 4
+        whole = n <= sample or used + 4 * n + rest <= budget
+        used += 4 * (n if whole else sample)
+        plan.append((name, whole))
+    return plan
+
+
+def dump_outputs(out_dir, outs):
+    """What the last timed step returned -- one EvalModel.forward 5-tuple per sequence -- as out_dir/<name>.npy, float32.  Alpha and
+    trimap first, so they are the ones written whole; an output too large for the budget is written as <name>_sample.npy: the
+    values at DUMP_SAMPLE positions of its flattened array drawn by numpy's default_rng(0), the same positions for the same shape
+    in every run.  With --batch B > 1 the names carry the sequence: seq<b>_<name>.
+    The inputs are the same in every run; the kernel configurations are not: each process times them at plan time, and two runs
+    that chose differently part well beyond rounding over the 100-frame clip (1080p: a tenth of the alpha values by > 1e-3).  For
+    output-by-output comparisons give both runs one OTVM_TUNE_FILE (the first saves its choices, the next loads them: bit-identical
+    dumps)."""
+    os.makedirs(out_dir, exist_ok=True)
+    pre = (lambda b: "") if len(outs) == 1 else (lambda b: "seq%d_" % b)
+    order = ("preds_alpha", "preds_trimap", "scaled_imgs", "tri_gt", "scaled_gts")
+    arrays = [(pre(b) + k, o[OUTPUT_NAMES.index(k)]) for k in order for b, o in enumerate(outs)]
+    for (name, x), (_, whole) in zip(arrays, dump_plan([(n, tuple(x.shape)) for n, x in arrays])):
+        v = x.detach().float().cpu().numpy()
+        if not whole:
+            idx = np.sort(np.random.default_rng(0).choice(v.size, DUMP_SAMPLE, replace=False))
+            v, name = v.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -207,9 +247,17 @@ def main():
                     help="BASELINE configs[4] stress variant: memorise EVERY frame, never evict (max_memory_num = T)")
     ap.add_argument("--per-frame-report", default=None,
                     help="write per-frame device time (HIP events between frames) and slots read (JSON) to this path")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (the 5-tuple of EvalModel.forward) as "
+                         "DIR/<name>.npy, float32, at most 64 MB in all (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra legs after the headline: roofline (per-launch HIP events, live PMC traffic), CPU "
+                         "baseline, the f16 mode's alpha error against f16x3")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline leg")
     args = ap.parse_args()
+    if args.layer_report and not args.full:
+        ap.error("--layer-report comes from the roofline leg: add --full")
 
     # --gpus N > 1 outside a torch.distributed launch: start the N ranks ourselves (one process per GPU, RCCL)
     from otvm_amd.dist import self_launch_command
@@ -267,10 +315,11 @@ def main():
             # so the query encoder of frame t may start while frame t-1's alpha network is still executing
             h0 = time.perf_counter()
             if NB == 1:
-                out = model(a, frames[t], frames[t], tri=None, tri_gt=tri, large_input=False, _inputs_ready=True, **fkw(t))
+                outs = [model(a, frames[t], frames[t], tri=None, tri_gt=tri, large_input=False, _inputs_ready=True, **fkw(t))]
             else:
                 fr = [c[t] for c in clips]
-                out = model.forward_batch([a] * NB, fr, fr, [tri] * NB, large_input=False, _inputs_ready=True, **fkw(t))[0]
+                outs = model.forward_batch([a] * NB, fr, fr, [tri] * NB, large_input=False, _inputs_ready=True, **fkw(t))
+            out = outs[0]
             if not (t == T - 1):          # (the clip's last frame ends with the range guard's synchronising read: not issue time)
                 host_issue[0] += time.perf_counter() - h0
                 host_issue[1] += 1
@@ -280,7 +329,7 @@ def main():
                 frame_ev[t].record()
             if sink is not None:
                 sink.append(out[3])
-        return out
+        return outs
 
     def sync_all():
         torch.cuda.synchronize(dev)
@@ -293,11 +342,13 @@ def main():
     sync_all()
     host_issue[0], host_issue[1] = 0.0, 0
     t_start = time.perf_counter()
-    out = run_frames(lead_in + Wm, T)
+    last_outs = run_frames(lead_in + Wm, T)
     sync_all()
     elapsed = time.perf_counter() - t_start
-    alpha_last = out[3]
+    alpha_last = last_outs[0][3]
     host_issue_s = host_issue[0] * K / max(1, host_issue[1])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_outs)
 
     per_rank = None
     if dist is not None:
@@ -373,7 +424,7 @@ def main():
                 for i, t in enumerate(ts) if i > 0 and t >= lead_in + Wm]
         json.dump(dict(workload=result["config"]["workload"], padded=[Hp, Wp], hw=hw, frames=rows), open(args.per_frame_report, "w"), indent=0)
 
-    if rank == 0 and not args.no_roofline:          # (N > 1: the other ranks wait in the final barrier)
+    if rank == 0 and args.full and not args.no_roofline:          # (N > 1: the other ranks wait in the final barrier)
         # instrumented replay of a window of steady-state frames: HIP events around each conv launch
         nrep = min(K, 10)
         eng.prof = []
@@ -471,7 +522,7 @@ def main():
             if mr_block is not None:
                 result["memory_read"] = mr_block
 
-    if rank == 0 and world == 1 and NB == 1 and eng.precision_name == "f16":
+    if rank == 0 and args.full and world == 1 and NB == 1 and eng.precision_name == "f16":
         # the labelled single-pass mode reports what it costs in accuracy: the first frames of the same clip through an f16x3 model
         # (the parity-graded configuration) and through this one, alpha against alpha
         nerr = min(T, 26)
@@ -496,7 +547,7 @@ def main():
                     "(tests/), this mode does not claim to"}
         del m3
 
-    if rank == 0 and world == 1 and NB == 1 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and world == 1 and NB == 1 and not args.no_cpu_baseline:
         # CPU baseline: the oracle (port of the reference algorithm) on the host cores, ONE steady-state frame of the
         # same clip at full resolution; its bank is seeded from the device bank so no CPU warm-up frames are needed.
         from oracle.otvm_oracle import OtvmOracle

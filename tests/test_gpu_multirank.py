@@ -125,7 +125,7 @@ def test_bench_measures_conv_traffic_live(tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "OTVM_BENCH_LIVE_PMC"):
         env.pop(k, None)
     env["OTVM_TUNE_FILE"] = os.path.join(str(tmp_path), "tune.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
                         "--height", "480", "--width", "832"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -141,6 +141,32 @@ def test_bench_measures_conv_traffic_live(tmp_path):
         assert 0.9 < ratio < 2.0, (ratio, src)
     else:
         assert src is not None and "not available" in src, src
+
+
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """A plain `bench.py` (no --full) times the steps and prints the headline only: no roofline, CPU baseline or f16 leg.
+    --dump-outputs writes the 5-tuple of the last timed step as float32 .npy files; the alpha file is the alpha the line's
+    checksum was taken from."""
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    env["OTVM_TUNE_FILE"] = os.path.join(str(tmp_path), "tune.json")
+    d = os.path.join(str(tmp_path), "outputs")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                        "--height", "480", "--width", "832", "--dump-outputs", d],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["warmup"] == 2 and line["ms_per_step"] > 0
+    assert abs(line["value"] - 1000.0 / line["ms_per_step"]) <= 1e-6 * line["value"]
+    assert not {"roofline", "cpu_baseline", "alpha_error_vs_f16x3", "memory_read"} & set(line), sorted(line)
+    files = sorted(os.listdir(d))
+    assert files == sorted(n + ".npy" for n in ("preds_alpha", "preds_trimap", "scaled_imgs", "tri_gt", "scaled_gts")), files
+    assert sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64 * 10 ** 6
+    alpha = np.load(os.path.join(d, "preds_alpha.npy"))
+    assert alpha.dtype == np.float32 and alpha.shape == (1, 1, 1, 480, 832)
+    assert np.isfinite(alpha).all() and 0.0 <= alpha.min() and alpha.max() <= 1.0
+    assert abs(float(alpha.astype(np.float64).mean()) - line["alpha_checksum"]) <= 1e-9
 
 
 def test_rccl_with_one_rank_through_bench_and_eval_cli(tmp_path):

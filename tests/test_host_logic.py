@@ -480,3 +480,55 @@ def test_bench_sums_the_conv_rows_of_a_counter_file(tmp_path):
     assert bench.sum_conv_counter(str(p), "FETCH_SIZE") == (1510.5, 3)
     assert bench.sum_conv_counter(str(p), "WRITE_SIZE") == (9.0, 1)
     assert bench.sum_conv_counter(str(p), "SQ_WAVES") == (0.0, 0)
+
+
+def test_bench_dumps_the_last_step_within_64_mb(tmp_path):
+    """bench.py::dump_outputs (--dump-outputs DIR): the 5-tuple of EvalModel.forward as DIR/<name>.npy, float32, 64 MB at most in
+    all.  At 1920x1080 alpha and trimap are written whole, outputs that do not fit as a sample at fixed positions; a second call
+    on other values writes the same file names with the values at the same positions."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_for_test3", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    H, W = 1080, 1920
+
+    def step(seed):
+        g = torch.Generator().manual_seed(seed)
+        shapes = dict(scaled_imgs=(1, 1, 3, H, W), preds_trimap=(1, 1, 3, H, W), tri_gt=(1, 1, 3, H, W),
+                      preds_alpha=(1, 1, 1, H, W), scaled_gts=(1, 1, 1, H, W))
+        return tuple(torch.rand(shapes[n], generator=g) for n in bench.OUTPUT_NAMES)
+
+    outs = [step(1)]
+    d1, d2 = str(tmp_path / "a"), str(tmp_path / "b")
+    bench.dump_outputs(d1, outs)
+    files = sorted(os.listdir(d1))
+    assert files == ["preds_alpha.npy", "preds_trimap.npy", "scaled_gts.npy", "scaled_imgs_sample.npy", "tri_gt_sample.npy"], files
+    assert sum(os.path.getsize(os.path.join(d1, f)) for f in files) <= 64 * 10 ** 6
+    for f in files:
+        assert np.load(os.path.join(d1, f)).dtype == np.float32
+    alpha = np.load(os.path.join(d1, "preds_alpha.npy"))
+    assert alpha.shape == (1, 1, 1, H, W) and np.array_equal(alpha, outs[0][3].numpy())
+    s1 = np.load(os.path.join(d1, "tri_gt_sample.npy"))
+    assert s1.shape == (bench.DUMP_SAMPLE,)
+    # the positions depend on the shape only: the sample of a tensor whose values ARE their positions names them
+    o2 = list(step(2))
+    o2[2] = torch.arange(3 * H * W, dtype=torch.float64).reshape(1, 1, 3, H, W)
+    bench.dump_outputs(d2, [tuple(o2)])
+    idx = np.load(os.path.join(d2, "tri_gt_sample.npy")).astype(np.int64)
+    assert (np.diff(idx) > 0).all() and np.array_equal(s1, outs[0][2].numpy().reshape(-1)[idx])
+    # a lock-step batch: names carry the sequence, the budget holds
+    d3 = str(tmp_path / "c")
+    bench.dump_outputs(d3, [step(3), step(4)])
+    files = os.listdir(d3)
+    assert "seq0_preds_alpha.npy" in files and "seq1_preds_alpha.npy" in files and len(files) == 10
+    assert sum(os.path.getsize(os.path.join(d3, f)) for f in files) <= 64 * 10 ** 6
+
+
+def test_bench_layer_report_needs_full():
+    """The per-layer table comes from the roofline leg, which only a --full run executes: asking for it without --full is an
+    argument error, not a silently missing file."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--layer-report", os.devnull],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--full" in r.stderr, r.stderr[-2000:]

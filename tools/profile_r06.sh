@@ -7,8 +7,8 @@ R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/prof_r06; mkdir -p $O
 export OTVM_TUNE_FILE=$O/tune_cache.json
 cd $R
-python bench.py --layer-report $O/layers_1080p.json --tune-report $O/tune_1080p.json > $O/bench_1080p.json 2> $O/bench_1080p.err
-python bench.py --height 480 --width 832 --steps 47 --warmup 3 --layer-report $O/layers_480p.json --tune-report $O/tune_480p.json > $O/bench_480p.json 2> $O/bench_480p.err
+python bench.py --full --layer-report $O/layers_1080p.json --tune-report $O/tune_1080p.json > $O/bench_1080p.json 2> $O/bench_1080p.err
+python bench.py --full --height 480 --width 832 --steps 47 --warmup 3 --layer-report $O/layers_480p.json --tune-report $O/tune_480p.json > $O/bench_480p.json 2> $O/bench_480p.err
 cd /tmp && export TMPDIR=/tmp
 CMD="python $R/bench.py --steps 20 --warmup 3 --clip-frames 23 --no-cpu-baseline --no-roofline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks1080 -o ks -- $CMD > $O/ks1080.log 2>&1
@@ -29,9 +29,9 @@ python tools/pmc_traffic.py $FC $WC 11 > $O/conv_traffic_1080p.json 2>$O/traffic
 python tools/pmc_glue_traffic.py $O/fetch $O/write 11 > $O/kernel_traffic_gbps_1080p.md 2>>$O/traffic.err
 python tools/layer_roofline_md.py $O/layers_1080p.json "1920x1080 (bench.py default run)" > $O/layer_roofline_1080p.md 2>&1
 python tools/layer_roofline_md.py $O/layers_480p.json "832x480" > $O/layer_roofline_480p.md 2>&1
-python bench.py --precision f16 --no-cpu-baseline --layer-report $O/layers_f16_1080p.json > $O/bench_f16_1080p.json 2> $O/bench_f16.err
-python bench.py --batch 2 --steps 40 --warmup 5 --no-cpu-baseline > $O/bench_1080p_batch2.json 2> $O/bench_b2.err
-python bench.py --height 480 --width 832 --batch 4 --steps 47 --warmup 3 --no-cpu-baseline > $O/bench_480p_batch4.json 2> $O/bench_480b4.err
+python bench.py --full --precision f16 --no-cpu-baseline --layer-report $O/layers_f16_1080p.json > $O/bench_f16_1080p.json 2> $O/bench_f16.err
+python bench.py --full --batch 2 --steps 40 --warmup 5 --no-cpu-baseline > $O/bench_1080p_batch2.json 2> $O/bench_b2.err
+python bench.py --full --height 480 --width 832 --batch 4 --steps 47 --warmup 3 --no-cpu-baseline > $O/bench_480p_batch4.json 2> $O/bench_480b4.err
 rm -f $O/ab_1080p.txt
 PL=$R/otvm_amd/libotvm_hip_probes.so
 for v in "OTVM_FUSE_STM_BLOCK128=1" "OTVM_FUSE_STM_BLOCK128=0" "OTVM_GN_PREDICT=0" "OTVM_FUSE_HEAD=0" "OTVM_FUSE_STM_BLOCK128=1" "OTVM_FUSE_STM_BLOCK128=0"; do
@@ -48,7 +48,7 @@ done
 (cd _prev 2>/dev/null && unset OTVM_TUNE_FILE && OTVM_BENCH_LIVE_PMC=0 python bench.py --height 480 --width 832 --steps 47 --warmup 3 --no-cpu-baseline --no-roofline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('round-5 tree (5b5c5c4), same box, 832x480', round(d['value'],2), 'frames/s')" >> $O/ab_1080p.txt)
 cat $O/ab_1080p.txt
 # BASELINE configs[4]: 3840x2160, T=200, every frame memorised, nothing evicted
-(unset OTVM_TUNE_FILE; OTVM_BENCH_LIVE_PMC=1 python bench.py --height 2160 --width 3840 --steps 197 --warmup 3 --stress-bank --no-cpu-baseline > $O/bench_4k_T200_growing.json 2> $O/bench_4k.err)
+(unset OTVM_TUNE_FILE; OTVM_BENCH_LIVE_PMC=1 python bench.py --full --height 2160 --width 3840 --steps 197 --warmup 3 --stress-bank --no-cpu-baseline > $O/bench_4k_T200_growing.json 2> $O/bench_4k.err)
 head -c 300 $O/bench_4k_T200_growing.json; echo
 find $O -name "*kernel_trace.csv" -delete; find $O -name "*counter_collection.csv" -delete; find $O -name "*agent_info.csv" -delete
 cat $O/bench_1080p.json | head -c 700; echo; cat $O/bench_480p.json | head -c 300; echo; head -c 400 $O/bench_f16_1080p.json; echo
