@@ -40,7 +40,7 @@ extern "C" {
 #define OTVM_PREC_F16 2
 
 const char* otvm_last_error(void);
-#define OTVM_ABI_VERSION 19   /* 2: otvm_ppm_pool_ws_bytes(H, C); 3: otvm_conv_params.in_scale/in_shift/in_act;
+#define OTVM_ABI_VERSION 20   /* 2: otvm_ppm_pool_ws_bytes(H, C); 3: otvm_conv_params.in_scale/in_shift/in_act;
                                  4: otvm_conv_params.splitk_ws; 5: otvm_preprocess_params.fg_u8/bg_u8/u8_rgb;
                                  6: otvm_conv_params.tune + otvm_conv2d_candidates;
                                  7: folded GroupNorm tables on otvm_gn_apply's residual and otvm_upsample_bilinear's input;
@@ -59,7 +59,8 @@ const char* otvm_last_error(void);
                                      from its input's Gram matrix: the normalisation moves into that convolution's epilogue);
                                  18: otvm_gram_params.diag / otvm_gn_predict_params.diag (conditioning + saturation diagnostics of the
                                      predicted statistics); implicit-GEMM tiles 32 + t with LDS-DMA weight stages and 64 + t = the same on
-                                     v_mfma_f32_16x16x32_f16 (tune codes; no new entry points) */
+                                     v_mfma_f32_16x16x32_f16 (tune codes; no new entry points);
+                                 20: otvm_matting_grad_conn / _ws_bytes / _params (Grad and Conn matting metrics) */
 int otvm_abi_version(void);
 
 /* ---------------------------------------------------------------- weights (load time) ----------
@@ -450,6 +451,19 @@ int otvm_onehot_argmax3(const float* tri, int64_t P, float* out, void* stream);
  * caller-zeroed) accumulates  sum|p-t|m, sum(p-t)^2 m, sum m, sum((p-p')-(t-t'))^2 m', sum m'  -- integer-exact. */
 int otvm_matting_metrics(const uint8_t* pred, const uint8_t* target, const uint8_t* mask, const uint8_t* prev_pred,
                          const uint8_t* prev_target, const uint8_t* prev_mask, int64_t n, double* acc, void* stream);
+/* Grad and Conn of one frame (reference utils/tmp/metric.py:16-46,191-234) on the same 8-bit alphas and optional {0,1} mask
+ * (NULL = all pixels).  acc[2] (fp64, caller-zeroed) accumulates  Grad = sum (|grad p| - |grad t|)^2 m  (9x9 Gaussian
+ * derivative of sigma 1.4, replicate padding) and  Conn = sum |phi_p - phi_t| m  (10 thresholds, largest 4-connected
+ * component of each, ties to the component with the smallest first raster index).  level_map (optional, uint8 [H,W])
+ * receives each pixel's Conn level: k for t_k = float32 0.1 k, 10 for 1.0.  ws: otvm_matting_grad_conn_ws_bytes(H, W)
+ * bytes of device memory, no initialisation needed; one ws serves one stream at a time.                            */
+int otvm_matting_grad_conn(const uint8_t* pred, const uint8_t* target, const uint8_t* mask, int H, int W, double* acc,
+                           uint8_t* level_map, void* ws, void* stream);
+int64_t otvm_matting_grad_conn_ws_bytes(int H, int W);
+/* host-side constants of the kernel above: cutoffs[10] = c_i (pred, target >= c_i <=> x/255.f >= t_i, i = 1..10),
+ * levels[11] = t_k as float32, taps[18] = the L2-normalised 1-D Gaussian [9] and Gaussian-derivative [9] factors of hx.
+ * Any pointer may be NULL.                                                                                           */
+int otvm_matting_grad_conn_params(int* cutoffs, float* levels, double* taps);
 
 /* ---------------------------------------------------------------- range guard / clear -----------
  * f16x3 splits fp32 operands into fp16 halves: |x| >= 65504 loses accuracy, >= 131008 becomes inf.

@@ -32,6 +32,7 @@ SOURCES = [
     ("memory_read.hip", []),
     ("memory_read_f16x3.hip", []),
     ("metrics.hip", []),
+    ("metrics_grad_conn.hip", ["-ffp-contract=off"]),
     ("guard.hip", []),
     ("losses.hip", ["-ffp-contract=off"]),
 ]

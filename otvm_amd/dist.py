@@ -188,7 +188,7 @@ def run_sharded(sequences, matte_fn, rank=0, world=1, device="cpu", reference_fn
     # err^2 / (mask_sum + 1); :252-264: dtSSD = per-pair sqrt(err^2) with its own normaliser), so the reduced report
     # carries the numbers the reference's BatchMetric would print, not only pooled ratios
     keys = ("frames", "sad_sum", "mse_num", "mask_sum", "dt_err2_sum", "dt_mask_sum", "mse_frame_sum", "dtssd_pair_sum", "dtssd_norm_sum",
-            "pairs")
+            "pairs", "img_frames", "grad_sum", "conn_sum", "ssda_frame_sum")
     clip = [0.0] * len(keys)
     for out in outputs.values():
         m = out.get("metrics") if isinstance(out, dict) else None
@@ -199,6 +199,11 @@ def run_sharded(sequences, matte_fn, rank=0, world=1, device="cpu", reference_fn
             m["dtssd_pair_sum"] = float(sum(dt))                             # the (error, num) pairs dtSSD returns
             m["dtssd_norm_sum"] = float(sum(e / n for e, n in zip(dt, dn)))
             m["pairs"] = float(len(dt))
+            # Grad / Conn / SSDA (ClipMetrics(image_metrics=True)); clips without them add nothing
+            img = "grad_sum" in m
+            m["img_frames"] = float(m["frames"]) if img else 0.0
+            m["grad_sum"], m["conn_sum"] = float(m.get("grad_sum", 0.0)), float(m.get("conn_sum", 0.0))
+            m["ssda_frame_sum"] = float(sum(m.get("ssda_per_frame", [])))
             clip = [c + float(m[k]) for c, k in zip(clip, keys)]
     red, (maxabs_g, wall_g) = reduce_metrics([sad, frames, secs] + clip, [maxabs, secs], device)
     sad_g, frames_g, secs_sum = red[:3]
@@ -221,4 +226,8 @@ def run_sharded(sequences, matte_fn, rank=0, world=1, device="cpu", reference_fn
                                      dtssd_mean=g["dtssd_pair_sum"] / max(1.0, g["pairs"]),       # mean of the per-pair errors
                                      dtssd_norm_mean=g["dtssd_norm_sum"] / max(1.0, g["pairs"]),  # ... of error / num
                                      dtssd_sum_err2=g["dt_err2_sum"], dtssd_mask_sum=g["dt_mask_sum"])
+        if g["img_frames"] > 0:
+            # per-frame means of BatchGradient / BatchConnectivity (no /1000) and of SSDA's error (metric.py:191-250)
+            summary["gt_metrics"].update(grad_mean=g["grad_sum"] / g["img_frames"], conn_mean=g["conn_sum"] / g["img_frames"],
+                                         ssda_mean=g["ssda_frame_sum"] / g["img_frames"])
     return summary

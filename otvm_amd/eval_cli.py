@@ -7,7 +7,7 @@
 Dataset layouts: otvm_amd/datasets.py (Demo_Test / VideoMatting108_Test, reference dataset.py:959-1070).  Without
 --demo the VideoMatting108 validation split is evaluated as eval.py:86-89 does: the first-frame trimap is derived
 from the ground-truth alpha with the --trimap dilation, and SAD / MSE / dtSSD against the ground truth are
-accumulated on the device and reduced over ranks.  Alpha PNGs are written as trunc(alpha*255) (eval.py:209-217);
+accumulated on the device and reduced over ranks (--all-metrics: also Grad, Conn and SSDA).  Alpha PNGs are written as trunc(alpha*255) (eval.py:209-217);
 --viz adds the six-panel composite frames (eval.py:96-115) and, when ffmpeg exists, the mp4 (eval.py:229-242).
 Frame IO runs through otvm_amd/io_pipeline.py: the demo flow decodes ahead in a thread pool and uploads on a copy
 stream, both flows download the 8-bit alphas asynchronously and PNG-encode them in a pool (the reference's loop blocks
@@ -47,6 +47,8 @@ def main(argv=None):
                          "frames are decoded up front in this mode).  Default: 1 for a single rank; a multi-rank run "
                          "(--gpus N / torchrun: a throughput run, configs[3]) picks 2 at 1080p and 4 at <= 480p "
                          "(dist.default_batch; measured +5 % / +41 % aggregate)")
+    ap.add_argument("--all-metrics", action="store_true",
+                    help="VideoMatting108: also Grad, Conn and SSDA against the ground truth (device kernels, metric.py:191-250)")
     ap.add_argument("--summary-json", default=None, help="rank 0 writes the reduced summary (frames, fps, metrics, shards) here")
     args = ap.parse_args(argv)
     from PIL import Image
@@ -166,7 +168,8 @@ def main(argv=None):
         else:
             res = run_video_matte(model, data["frames"], alphas=data["alphas"], backgrounds=data["backgrounds"],
                                   skip=args.skip, max_num=args.max_num, on_frame=save, device=dev,
-                                  gt_alpha_u8=data["gt_alpha_u8"], gt_mask="unknown", keep_on_device=True)
+                                  gt_alpha_u8=data["gt_alpha_u8"], gt_mask="unknown", keep_on_device=True,
+                                  gt_image_metrics=args.all_metrics)
         if writer is not None:
             writer.close()
         if args.viz:
@@ -191,7 +194,8 @@ def main(argv=None):
             res = run_video_matte_batch(model, [d["frames"] for d in datas], alphas=[d["alphas"] for d in datas],
                                         backgrounds=[d["backgrounds"] for d in datas], skip=args.skip, max_num=args.max_num,
                                         on_frame=save, device=dev, keep_on_device=True,
-                                        gt_alpha_u8=[d["gt_alpha_u8"] for d in datas], gt_mask="unknown")
+                                        gt_alpha_u8=[d["gt_alpha_u8"] for d in datas], gt_mask="unknown",
+                                        gt_image_metrics=args.all_metrics)
         for w in writers:
             w.close()
         return res
@@ -221,8 +225,11 @@ def main(argv=None):
         print("done | %d frames | %.2f frames/s over %d GPU(s)" % (summary["frames"], summary["fps"], world))
         if "gt_metrics" in summary:
             g = summary["gt_metrics"]
-            print("vs ground truth (unknown band) | SAD/frame %.4f | MSE/frame %.6f (pooled %.6f) | dtSSD/pair %.6f | frames %d"
-                  % (g["sad"], g["mse_mean"], g["mse"], g["dtssd_mean"], g["frames"]))
+            extra = ""
+            if "grad_mean" in g:
+                extra = " | Grad/frame %.4f | Conn/frame %.4f | SSDA/frame %.6f" % (g["grad_mean"], g["conn_mean"], g["ssda_mean"])
+            print("vs ground truth (unknown band) | SAD/frame %.4f | MSE/frame %.6f (pooled %.6f) | dtSSD/pair %.6f%s | frames %d"
+                  % (g["sad"], g["mse_mean"], g["mse"], g["dtssd_mean"], extra, g["frames"]))
     return summary
 
 

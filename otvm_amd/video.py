@@ -47,7 +47,7 @@ def _as_tensor(x):
 
 def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, skip=10, max_num=5,
                     frames_are_rgb=False, on_frame=None, device=None, keep_on_device=False, gt_alpha_u8=None,
-                    gt_mask_u8=None, gt_mask=None):
+                    gt_mask_u8=None, gt_mask=None, gt_image_metrics=False):
     """Matte one sequence.
 
     model       : EvalModel (optionally wrapped in nn.DataParallel), on the GPU
@@ -57,7 +57,8 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                   from alpha with the model's dilate kernel) -- required when trimap is None
     gt_alpha_u8 : optional per-frame ground-truth alpha, uint8 [H,W]; with it SAD/MSE/dtSSD are accumulated on
                   the device (ClipMetrics) and returned under "metrics"; gt_mask_u8 = optional {0,1} evaluation masks,
-                  gt_mask="unknown" = the reference metric's default mask (0 < gt < 255) instead
+                  gt_mask="unknown" = the reference metric's default mask (0 < gt < 255) instead; gt_image_metrics=True adds
+                  Grad, Conn and SSDA (ClipMetrics(image_metrics=True))
     backgrounds : optional per-frame BG images (V108 composites fg*a + bg*(1-a)), same dtype / channel order as the
                   frames; default bg = fg
     Returns dict(alpha=[T,H,W] float32, alpha_u8=[T,H,W] uint8 (truncated, eval.py:209), trimap=[T,3,H,W],
@@ -68,7 +69,7 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
     dev = device or next(model.parameters()).device
     out_a, out_u8, out_t, bank_log = [], [], [], []
     core = model.module if hasattr(model, "module") else model
-    metrics = ClipMetrics(dev) if gt_alpha_u8 is not None else None
+    metrics = ClipMetrics(dev, image_metrics=gt_image_metrics) if gt_alpha_u8 is not None else None
     # loop invariants: the user trimap (25 MB as fp32 at 1080p) is uploaded once, not once per frame; the dummy alpha
     # of the trimap flow is one tensor for the whole clip
     tri_dev = None
@@ -149,13 +150,15 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
 
 
 def run_video_matte_batch(model, clips, trimaps=None, alphas=None, backgrounds=None, skip=10, max_num=5, frames_are_rgb=False,
-                          device=None, keep_on_device=False, on_frame=None, gt_alpha_u8=None, gt_mask=None):
+                          device=None, keep_on_device=False, on_frame=None, gt_alpha_u8=None, gt_mask=None,
+                          gt_image_metrics=False):
     """Matte B sequences of one resolution in LOCK-STEP (round 3): frame i of every clip goes through the network in one
     batched step (EvalModel.forward_batch: one launch per layer over the B images, per-sequence memory banks).
     clips: list of B frame arrays ([T_b,H,W,3] uint8 / float, BGR unless frames_are_rgb); trimaps: list of B first-frame
     one-hot trimaps [3,H,W] (demo flow) or None with alphas = list of B per-frame GT alpha lists (V108 flow: the first-frame
     trimap is derived from the alpha); backgrounds: optional list of B per-frame background lists; gt_alpha_u8: optional
-    list of B per-frame uint8 ground truths (SAD / MSE / dtSSD per clip, as run_video_matte); on_frame(b, i, alpha, u8, out).
+    list of B per-frame uint8 ground truths (SAD / MSE / dtSSD per clip, as run_video_matte; gt_image_metrics=True adds Grad,
+    Conn and SSDA); on_frame(b, i, alpha, u8, out).
     Clips may differ in LENGTH: the batch runs max(T_b) steps, a clip that has ended keeps feeding its last frame (its
     outputs from then on are discarded) -- sequences are independent (all recurrent state is per sequence), so
     this changes no result of the others; the frame flags follow the frame index, which the clips share.
@@ -172,7 +175,7 @@ def run_video_matte_batch(model, clips, trimaps=None, alphas=None, backgrounds=N
     core = model.module if hasattr(model, "module") else model
     dev = device or next(core.parameters()).device
     res = [dict(alpha=[], alpha_u8=[], trimap=[], bank_frames=[]) for _ in range(B)]
-    metrics = [ClipMetrics(dev) for _ in range(B)] if gt_alpha_u8 is not None else None
+    metrics = [ClipMetrics(dev, image_metrics=gt_image_metrics) for _ in range(B)] if gt_alpha_u8 is not None else None
     tri_dev = None if trimaps is None else [_as_tensor(t).to(dev).float()[None, None] for t in trimaps]
     ones = None
     for i in range(T):
@@ -247,13 +250,19 @@ class ClipMetrics:
     utils/tmp/metric.py:177-189,252-264 on the 8-bit alphas the path writes (eval.py:209).  One row of partial sums
     per frame stays on the device (no per-frame synchronisation); result() turns them into the reference's per-frame
     values.  mask: None = all pixels, "unknown" = the reference's default (0 < target < 255, metric.py:113-115), or
-    explicit uint8 {0,1} masks."""
+    explicit uint8 {0,1} masks.
+    image_metrics=True also runs otvm_matting_grad_conn per frame into a second row buffer on the same stream: result()
+    then adds Grad and Conn (BatchGradient / BatchConnectivity, metric.py:191-234, as they return them: no /1000) and SSDA
+    (metric.py:244-250: sqrt of the masked squared error / 255 and its count, from the SAD / MSE row)."""
 
-    def __init__(self, device, capacity=256):
+    def __init__(self, device, capacity=256, image_metrics=False):
         from . import lib as L
         self.L, self.lib = L, L.load()
         self.device = device
         self.acc = torch.zeros(capacity, 5, dtype=torch.float64, device=device)
+        self.image_metrics = bool(image_metrics)
+        self.acc_gc = torch.zeros(capacity, 2, dtype=torch.float64, device=device) if self.image_metrics else None
+        self.ws, self.ws_shape = None, None
         self.prev = None
         self.frames = 0
 
@@ -268,10 +277,20 @@ class ClipMetrics:
         mask_u8 = None if mask_u8 is None else mask_u8.contiguous()
         if self.frames == self.acc.shape[0]:
             self.acc = torch.cat([self.acc, torch.zeros_like(self.acc)])
+            if self.acc_gc is not None:
+                self.acc_gc = torch.cat([self.acc_gc, torch.zeros_like(self.acc_gc)])
         pp, tp, mp = self.prev if self.prev is not None else (None, None, None)
         ptr = lambda x: 0 if x is None else x.data_ptr()
         self.L.check(self.lib.otvm_matting_metrics(ptr(pred_u8), ptr(target_u8), ptr(mask_u8), ptr(pp), ptr(tp), ptr(mp),
                                                    pred_u8.numel(), self.acc[self.frames].data_ptr(), st), "matting_metrics")
+        if self.image_metrics:
+            H, W = pred_u8.shape[-2:]
+            if self.ws_shape != (H, W):            # stream-ordered re-use: the previous frame's launches come first
+                self.ws = torch.empty(self.lib.otvm_matting_grad_conn_ws_bytes(H, W), dtype=torch.uint8, device=pred_u8.device)
+                self.ws_shape = (H, W)
+            self.L.check(self.lib.otvm_matting_grad_conn(ptr(pred_u8), ptr(target_u8), ptr(mask_u8), H, W,
+                                                         self.acc_gc[self.frames].data_ptr(), None, self.ws.data_ptr(), st),
+                         "matting_grad_conn")
         self.prev = (pred_u8, target_u8, mask_u8)
         self.frames += 1
 
@@ -283,11 +302,17 @@ class ClipMetrics:
         # row i > 0 holds the temporal term of the pair (i-1, i), masked by frame i-1's mask (metric.py:252-264)
         dt_f = (rows[1:, 3] / 255.0 ** 2).sqrt().tolist()
         dt_n = (rows[1:, 4] + 1.0).tolist()
-        return dict(frames=self.frames, sad_sum=tot[0] / 255.0 / 1000.0, mse_num=tot[1] / 255.0 ** 2, mask_sum=tot[2],
-                    dt_err2_sum=tot[3] / 255.0 ** 2, dt_mask_sum=tot[4],
-                    sad_mean=tot[0] / 255.0 / 1000.0 / max(1, self.frames),
-                    sad_per_frame=sad_f, mse_per_frame=mse_f, dtssd_per_pair=dt_f, dtssd_num_per_pair=dt_n,
-                    dtssd_sum=float(sum(dt_f)))
+        res = dict(frames=self.frames, sad_sum=tot[0] / 255.0 / 1000.0, mse_num=tot[1] / 255.0 ** 2, mask_sum=tot[2],
+                   dt_err2_sum=tot[3] / 255.0 ** 2, dt_mask_sum=tot[4],
+                   sad_mean=tot[0] / 255.0 / 1000.0 / max(1, self.frames),
+                   sad_per_frame=sad_f, mse_per_frame=mse_f, dtssd_per_pair=dt_f, dtssd_num_per_pair=dt_n,
+                   dtssd_sum=float(sum(dt_f)))
+        if self.image_metrics:
+            gc = self.acc_gc[:self.frames].cpu()
+            res.update(grad_per_frame=gc[:, 0].tolist(), conn_per_frame=gc[:, 1].tolist(),
+                       grad_sum=float(gc[:, 0].sum()), conn_sum=float(gc[:, 1].sum()),
+                       ssda_per_frame=(rows[:, 1].sqrt() / 255.0).tolist(), ssda_num_per_frame=(rows[:, 2] + 1.0).tolist())
+        return res
 
 
 def sad(pred, ref, mask=None):
