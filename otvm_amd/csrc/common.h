@@ -108,6 +108,22 @@ __device__ __forceinline__ void otvm_static_for(F&& f) {
     otvm_static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
+// GroupNorm sums from a run of fp32 values accumulated as offsets from a pilot value p (s = sum(v - p), ss = sum((v - p)^2)
+// over n terms) -> fp64 sums of v and v^2.  The variance is E[v^2] - mean^2: summing v^2 itself in fp32 carries its rounding,
+// (mean / sd)^2 times larger, into the variance (gn_stats before the offsets, 1088x1920x64: 1.0e-4 relative at mean / sd = 100,
+// 4.9e-4 at 300; with them 3e-8 .. 1e-7, tests/test_gpu_size_paths.py); the offsets keep the fp32 run at the scale of the spread.
+// GN_CONV_PILOT: the fused conv epilogues reduce their fp32 runs across the lanes of a group before the fp64 step, so their pilot
+// must be one value per group: the bias of the group's first channel.  Each term is acc * scale + (bias - pilot) in one fma, so
+// the sums describe the output before its fp32 rounding (within 1e-11 relative of the written one).  The pilot removes an
+// offset that comes from the bias (the large mean of a conv output in practice); a conv without bias, or one whose mean comes
+// from its input, sums raw values as before.  A data pilot there would need the fp64 cross-lane reduction (measured: 1 % of a
+// 1080p frame).  The PPM head's fused statistics (resample.hip) still sum raw values.
+__device__ __forceinline__ void otvm_gn_unshift(float s, float ss, int n, float p, double& S, double& SS) {
+    const double pd = p, sd = s;
+    S = sd + (double)n * pd;
+    SS = (double)ss + pd * (2.0 * sd + (double)n * pd);
+}
+
 // ABI 16: the GroupNorm scale / shift table of a conv's OUTPUT, written by the last workgroup of the launch (see
 // otvm_conv_params.gn_counter).  Same arithmetic as gn_table_kernel (groupnorm.hip).
 struct OtvmGnTail {

@@ -819,14 +819,15 @@ void conv_igemm_f16x3_kernel(const Conv3Args pa) {
             // that share a column are lane ^ 16, lane ^ 32, lane ^ 48
 #pragma unroll
             for (int b = 0; b < TN; ++b) {
-                float s2[2], ss2[2];
+                float s2[2], ss2[2], c2[2];
 #pragma unroll
                 for (int sj = 0; sj < 2; ++sj) {
                     const int n = n0 + (wn * TN + b) * 32 + 16 * sj + (lane & 15);
-                    float s = 0.f, ss = 0.f;
+                    float s = 0.f, ss = 0.f, cnt = 0.f;        // offsets from the group's pilot (GN_CONV_PILOT, common.h)
+                    const float pil = n < p.Cout && p.bias ? p.bias[n / cg * cg] : 0.f;
                     if (n < p.Cout) {
                         const float sc_ = p.wscale[n];
-                        const float bias = p.bias ? p.bias[n] : 0.f;
+                        const float bias = p.bias ? p.bias[n] : 0.f, bd = bias - pil;   // the value minus the pilot in one fma
 #pragma unroll
                         for (int a = 0; a < TM; ++a)
 #pragma unroll
@@ -835,39 +836,48 @@ void conv_igemm_f16x3_kernel(const Conv3Args pa) {
                                 for (int r = 0; r < 4; ++r) {
                                     const int m = m0 + (wm * TM + a) * 32 + 16 * si + 4 * (lane >> 4) + r;
                                     if (m < p.M) {
-                                        const float v = acc[a][b][4 * (2 * si + sj) + r] * sc_ + bias;
-                                        s += v;
-                                        ss += v * v;
+                                        const float d = acc[a][b][4 * (2 * si + sj) + r] * sc_ + bd;
+                                        s += d;
+                                        ss += d * d;
+                                        cnt += 1.f;
                                     }
                                 }
                     }
-                    s += __shfl_xor(s, 16); ss += __shfl_xor(ss, 16);
-                    s += __shfl_xor(s, 32); ss += __shfl_xor(ss, 32);
-                    s2[sj] = s; ss2[sj] = ss;
+                    s += __shfl_xor(s, 16); ss += __shfl_xor(ss, 16); cnt += __shfl_xor(cnt, 16);
+                    s += __shfl_xor(s, 32); ss += __shfl_xor(ss, 32); cnt += __shfl_xor(cnt, 32);
+                    s2[sj] = s; ss2[sj] = ss; c2[sj] = cnt;
                 }
                 if (seg == 32) {                                // the tile's 32 columns lie in one group
-                    float s = s2[0] + s2[1], ss = ss2[0] + ss2[1];
+                    float s = s2[0] + s2[1], ss = ss2[0] + ss2[1], cnt = c2[0] + c2[1];
                     for (int off = 1; off < 16; off <<= 1) {
                         s += __shfl_xor(s, off);
                         ss += __shfl_xor(ss, off);
+                        cnt += __shfl_xor(cnt, off);
                     }
                     const int nl = (wn * TN + b) * 32;
                     if (lane == 0 && n0 + nl < p.Cout) {
-                        atomicAdd(&gred[2 * (nl / cg)], (double)s);
-                        atomicAdd(&gred[2 * (nl / cg) + 1], (double)ss);
+                        const float pil = p.bias ? p.bias[(n0 + nl) / cg * cg] : 0.f;
+                        double S, SS;
+                        otvm_gn_unshift(s, ss, (int)cnt, pil, S, SS);
+                        atomicAdd(&gred[2 * (nl / cg)], S);
+                        atomicAdd(&gred[2 * (nl / cg) + 1], SS);
                     }
                 } else {                                        // seg = cg <= 16 consecutive columns per group
 #pragma unroll
                     for (int sj = 0; sj < 2; ++sj) {
-                        float s = s2[sj], ss = ss2[sj];
+                        float s = s2[sj], ss = ss2[sj], cnt = c2[sj];
                         for (int off = 1; off < seg; off <<= 1) {
                             s += __shfl_xor(s, off);
                             ss += __shfl_xor(ss, off);
+                            cnt += __shfl_xor(cnt, off);
                         }
                         const int nl = (wn * TN + b) * 32 + 16 * sj + (lane & 15);
                         if (lane < 16 && (lane & (seg - 1)) == 0 && n0 + nl < p.Cout) {
-                            atomicAdd(&gred[2 * (nl / cg)], (double)s);
-                            atomicAdd(&gred[2 * (nl / cg) + 1], (double)ss);
+                            const float pil = p.bias ? p.bias[(n0 + nl) / cg * cg] : 0.f;
+                            double S, SS;
+                            otvm_gn_unshift(s, ss, (int)cnt, pil, S, SS);
+                            atomicAdd(&gred[2 * (nl / cg)], S);
+                            atomicAdd(&gred[2 * (nl / cg) + 1], SS);
                         }
                     }
                 }
@@ -877,32 +887,38 @@ void conv_igemm_f16x3_kernel(const Conv3Args pa) {
         for (int b = 0; b < TN; ++b) {
             const int nl = (wn * TN + b) * 32 + col;        // column inside the tile
             const int n = n0 + nl;
-            float s = 0.f, ss = 0.f;
+            float s = 0.f, ss = 0.f, cnt = 0.f;        // offsets from the group's pilot (GN_CONV_PILOT, common.h)
+            const float pil = n < p.Cout && p.bias ? p.bias[n / cg * cg] : 0.f;
             if (n < p.Cout) {
                 const float sc_ = p.wscale[n];
-                const float bias = p.bias ? p.bias[n] : 0.f;
+                const float bias = p.bias ? p.bias[n] : 0.f, bd = bias - pil;   // the value minus the pilot in one fma
 #pragma unroll
                 for (int a = 0; a < TM; ++a)
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
                         const int m = m0 + (wm * TM + a) * 32 + (e & 3) + 8 * (e >> 2) + rbase;
                         if (m < p.M) {
-                            const float v = acc[a][b][e] * sc_ + bias;
-                            s += v;
-                            ss += v * v;
+                            const float d = acc[a][b][e] * sc_ + bd;
+                            s += d;
+                            ss += d * d;
+                            cnt += 1.f;
                         }
                     }
             }
             s += __shfl_xor(s, 32);
             ss += __shfl_xor(ss, 32);
+            cnt += __shfl_xor(cnt, 32);
             for (int off = 1; off < seg; off <<= 1) {
                 s += __shfl_xor(s, off);
                 ss += __shfl_xor(ss, off);
+                cnt += __shfl_xor(cnt, off);
             }
             if (lane < 32 && (lane & (seg - 1)) == 0 && n < p.Cout) {
                 const int gl = nl / cg;                     // group index local to the tile
-                atomicAdd(&gred[2 * gl], (double)s);
-                atomicAdd(&gred[2 * gl + 1], (double)ss);
+                double S, SS;
+                otvm_gn_unshift(s, ss, (int)cnt, pil, S, SS);
+                atomicAdd(&gred[2 * gl], S);
+                atomicAdd(&gred[2 * gl + 1], SS);
             }
         }
         __syncthreads();

@@ -744,10 +744,11 @@ void conv_patch_f16x3_kernel(const PatchArgs pa) {
                 for (int sj = 0; sj < 2; ++sj) {
                     const int nl = (nt0 + b) * 32 + 16 * sj + (lane & 15);
                     const int n = n0 + nl;
-                    float s = 0.f, ss = 0.f;
+                    float s = 0.f, ss = 0.f, cnt = 0.f;        // offsets from the group's pilot (GN_CONV_PILOT, common.h)
+                    const float pil = n < p.Cout && p.bias ? p.bias[n / cg * cg] : 0.f;
                     if (n < p.Cout) {
                         const float sc_ = p.wscale[n];
-                        const float bias = p.bias ? p.bias[n] : 0.f;
+                        const float bias = p.bias ? p.bias[n] : 0.f, bd = bias - pil;   // the value minus the pilot in one fma
 #pragma unroll
                         for (int a = 0; a < TM; ++a) {
                             const int y = ty0 + wave_m * TM + a;
@@ -758,25 +759,29 @@ void conv_patch_f16x3_kernel(const PatchArgs pa) {
                                     const int e = 4 * (2 * si + sj) + j;
                                     const int x = tx0 + acc_row(e);
                                     if (y < p.H && x < p.W) {
-                                        const float v = acc[a][b][e] * sc_ + bias;
-                                        s += v;
-                                        ss += v * v;
+                                        const float d = acc[a][b][e] * sc_ + bd;
+                                        s += d;
+                                        ss += d * d;
+                                        cnt += 1.f;
                                     }
                                 }
                         }
                     }
-                    s += __shfl_xor(s, 16); ss += __shfl_xor(ss, 16);
-                    s += __shfl_xor(s, 32); ss += __shfl_xor(ss, 32);
+                    s += __shfl_xor(s, 16); ss += __shfl_xor(ss, 16); cnt += __shfl_xor(cnt, 16);
+                    s += __shfl_xor(s, 32); ss += __shfl_xor(ss, 32); cnt += __shfl_xor(cnt, 32);
                     const int seg16 = seg < 16 ? seg : 16;
                     for (int off = 1; off < seg16; off <<= 1) {
                         s += __shfl_xor(s, off);
                         ss += __shfl_xor(ss, off);
+                        cnt += __shfl_xor(cnt, off);
                     }
                     // (a group of 32 channels: its two 16-channel halves arrive as two atomics)
                     if (lane < 16 && (lane & (seg16 - 1)) == 0 && n < p.Cout) {
                         const int gl = nl / cg;
-                        atomicAdd(&gred[2 * gl], (double)s);
-                        atomicAdd(&gred[2 * gl + 1], (double)ss);
+                        double S, SS;
+                        otvm_gn_unshift(s, ss, (int)cnt, pil, S, SS);
+                        atomicAdd(&gred[2 * gl], S);
+                        atomicAdd(&gred[2 * gl + 1], SS);
                     }
                 }
         } else
@@ -784,10 +789,11 @@ void conv_patch_f16x3_kernel(const PatchArgs pa) {
         for (int b = 0; b < TN; ++b) {
             const int nl = (nt0 + b) * 32 + col;
             const int n = n0 + nl;
-            float s = 0.f, ss = 0.f;
+            float s = 0.f, ss = 0.f, cnt = 0.f;        // offsets from the group's pilot (GN_CONV_PILOT, common.h)
+            const float pil = n < p.Cout && p.bias ? p.bias[n / cg * cg] : 0.f;
             if (n < p.Cout) {
                 const float sc_ = p.wscale[n];
-                const float bias = p.bias ? p.bias[n] : 0.f;
+                const float bias = p.bias ? p.bias[n] : 0.f, bd = bias - pil;   // the value minus the pilot in one fma
 #pragma unroll
                 for (int a = 0; a < TM; ++a) {
                     const int y = ty0 + wave_m * TM + a;
@@ -795,23 +801,28 @@ void conv_patch_f16x3_kernel(const PatchArgs pa) {
                     for (int e = 0; e < 16; ++e) {
                         const int x = tx0 + (e & 3) + 8 * (e >> 2) + rbase;
                         if (y < p.H && x < p.W) {
-                            const float v = acc[a][b][e] * sc_ + bias;
-                            s += v;
-                            ss += v * v;
+                            const float d = acc[a][b][e] * sc_ + bd;
+                            s += d;
+                            ss += d * d;
+                            cnt += 1.f;
                         }
                     }
                 }
             }
             s += __shfl_xor(s, 32);
             ss += __shfl_xor(ss, 32);
+            cnt += __shfl_xor(cnt, 32);
             for (int off = 1; off < seg; off <<= 1) {
                 s += __shfl_xor(s, off);
                 ss += __shfl_xor(ss, off);
+                cnt += __shfl_xor(cnt, off);
             }
             if (lane < 32 && (lane & (seg - 1)) == 0 && n < p.Cout) {
                 const int gl = nl / cg;
-                atomicAdd(&gred[2 * gl], (double)s);
-                atomicAdd(&gred[2 * gl + 1], (double)ss);
+                double S, SS;
+                otvm_gn_unshift(s, ss, (int)cnt, pil, S, SS);
+                atomicAdd(&gred[2 * gl], S);
+                atomicAdd(&gred[2 * gl + 1], SS);
             }
         }
         __syncthreads();

@@ -263,10 +263,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 #pragma unroll
         for (int b = 0; b < TN; ++b) {
             const int n = b * 32 + col;
-            float s = 0.f, ss = 0.f;
+            float s = 0.f, ss = 0.f, cnt = 0.f;        // offsets from the group's pilot (GN_CONV_PILOT, common.h)
+            const float pil = n < p.Cout && p.bias ? p.bias[n / cg * cg] : 0.f;
             if (n < p.Cout) {
                 const float sc_ = p.wscale[n];
-                const float bias = p.bias ? p.bias[n] : 0.f;
+                const float bias = p.bias ? p.bias[n] : 0.f, bd = bias - pil;   // the value minus the pilot in one fma
 #pragma unroll
                 for (int a = 0; a < TM; ++a) {
                     const int y = ty0 + wave * TM + a;
@@ -274,23 +275,28 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
                     for (int e = 0; e < 16; ++e) {
                         const int x = tx0 + (e & 3) + 8 * (e >> 2) + rbase;
                         if (y < p.Ho && x < p.Wo) {
-                            const float v = acc[a][b][e] * sc_ + bias;
-                            s += v;
-                            ss += v * v;
+                            const float d = acc[a][b][e] * sc_ + bd;
+                            s += d;
+                            ss += d * d;
+                            cnt += 1.f;
                         }
                     }
                 }
             }
             s += __shfl_xor(s, 32);
             ss += __shfl_xor(ss, 32);
+            cnt += __shfl_xor(cnt, 32);
             for (int off = 1; off < seg; off <<= 1) {
                 s += __shfl_xor(s, off);
                 ss += __shfl_xor(ss, off);
+                cnt += __shfl_xor(cnt, off);
             }
             if (lane < 32 && (lane & (seg - 1)) == 0 && n < p.Cout) {
                 const int gl = n / cg;
-                atomicAdd(&gred[2 * gl], (double)s);
-                atomicAdd(&gred[2 * gl + 1], (double)ss);
+                double S, SS;
+                otvm_gn_unshift(s, ss, (int)cnt, pil, S, SS);
+                atomicAdd(&gred[2 * gl], S);
+                atomicAdd(&gred[2 * gl + 1], SS);
             }
         }
         __syncthreads();

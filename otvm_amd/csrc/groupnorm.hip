@@ -1,5 +1,5 @@
 // GroupNorm(32 groups, eps 1e-5, affine) on NHWC fp32 activations -- HBM-bound streaming kernels.
-//   stats : one pass, 16-byte loads, per-thread fp32 partials over a short pixel run, promoted to
+//   stats : one pass, 16-byte loads, per-thread fp32 partials over a short pixel run (offsets from the run's first pixel), promoted to
 //           fp64 for the block (LDS) and device (global atomic) reductions, so the result does not
 //           depend on the reduction order beyond fp64 rounding.
 //   apply : y = act((x - mean)*rstd*gamma + beta [+ residual]); per-channel scale/shift are built
@@ -23,26 +23,49 @@ __global__ void gn_stats_kernel(const float* __restrict__ x, int64_t P, int C, i
     const int q = threadIdx.x % Q, r = threadIdx.x / Q;
     if (threadIdx.x < G * 2) red[threadIdx.x] = 0.0;
     __syncthreads();
-    f32x4 s = {0.f, 0.f, 0.f, 0.f}, ss = {0.f, 0.f, 0.f, 0.f};
-    if (r < rows) {
-        for (int64_t pix = (int64_t)blockIdx.x * rows + r; pix < P; pix += (int64_t)gridDim.x * rows) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(x + pix * ld + q * 4);
+    // the fp32 run sums offsets from the thread's first pixel (otvm_gn_unshift): E[x^2] - mean^2 stays exact to fp32 rounding
+    // of the spread whatever the mean (plain sums of x^2: 1e-4 relative variance error at mean / sd = 100, 1080p)
+    f32x4 s = {0.f, 0.f, 0.f, 0.f}, ss = {0.f, 0.f, 0.f, 0.f}, p0 = {0.f, 0.f, 0.f, 0.f};
+    int n = 0;
+    const int64_t pix0 = (int64_t)blockIdx.x * rows + r, step = (int64_t)gridDim.x * rows;
+    if (r < rows && pix0 < P) {
+        p0 = *reinterpret_cast<const f32x4*>(x + pix0 * ld + q * 4);     // the pilot's own offset is 0: the loop starts after it
+        n = (int)((P - 1 - pix0) / step) + 1;
+        int64_t pix = pix0 + step;
+        // four independent loads in flight per thread (the grid is capped at 512 workgroups, 2 per CU): 135 -> 87 us per launch at
+        // 1088x1920x64, 529 -> 340 us at x256 (one load per iteration before; torch.cuda.Event pairs over 200 launches, MI355X)
+        for (; pix + 3 * step < P; pix += 4 * step) {
+            f32x4 v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = *reinterpret_cast<const f32x4*>(x + (pix + j * step) * ld + q * 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                v[j] -= p0;
+                s += v[j];
+                ss += v[j] * v[j];
+            }
+        }
+        for (; pix < P; pix += step) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(x + pix * ld + q * 4) - p0;
             s += v;
             ss += v * v;
         }
     }
     const int cg = C / G;                         // channels per group (>= 2)
-    if (r < rows) {
+    if (r < rows && n > 0) {
+        double S[4], SS[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) otvm_gn_unshift(s[j], ss[j], n, p0[j], S[j], SS[j]);
         if ((cg & 3) == 0) {                      // a float4 lies inside one group
             const int g = (q * 4) / cg;
-            atomicAdd(&red[g * 2], (double)s.x + (double)s.y + (double)s.z + (double)s.w);
-            atomicAdd(&red[g * 2 + 1], (double)ss.x + (double)ss.y + (double)ss.z + (double)ss.w);
+            atomicAdd(&red[g * 2], S[0] + S[1] + S[2] + S[3]);
+            atomicAdd(&red[g * 2 + 1], SS[0] + SS[1] + SS[2] + SS[3]);
         } else {                                  // cg = 2, 6, 10, ...: a float4 straddles groups -> per channel
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int g = (q * 4 + j) / cg;
-                atomicAdd(&red[g * 2], (double)s[j]);
-                atomicAdd(&red[g * 2 + 1], (double)ss[j]);
+                atomicAdd(&red[g * 2], S[j]);
+                atomicAdd(&red[g * 2 + 1], SS[j]);
             }
         }
     }

@@ -599,6 +599,8 @@ __global__ __launch_bounds__(256) void ppm_add_kernel(const float* __restrict__ 
         }
     }
     if (gn_stats) {
+        // (raw values, not offsets from a pilot as in gn_stats / the conv epilogues: the variance loses (mean / sd)^2 times the fp32
+        // rounding of these runs; common.h, otvm_gn_unshift)
         // 256 channels in 32 groups of 8: lanes 8k .. 8k+7 share a group; per-thread partial sums in fp32 over <= W / 2 pixels,
         // promoted to fp64 for the workgroup (LDS) and device (atomic) reductions
         for (int off = 1; off < 8; off <<= 1) {

@@ -532,3 +532,33 @@ def test_bench_layer_report_needs_full():
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--layer-report", os.devnull],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 2 and "--full" in r.stderr, r.stderr[-2000:]
+
+
+# ---- size-selected kernel paths: the coverage of tests/test_gpu_size_paths.py (rules restated in tests/size_paths.py)
+def test_size_path_cases_reach_every_selected_path():
+    """The EDT cases of tests/test_gpu_size_paths.py run every column kernel and the memory-read cases run multi-tile chunks that
+    cross slot boundaries; the partial count restated here equals the library's (host-only, no GPU needed)."""
+    from tests.size_paths import EDT_CASES, MR_SHAPES, edt_column_path, mr_launches
+    assert [edt_column_path(h) for h in (512, 513, 1280, 1281, 2560, 2561)] == ["8", "20", "20", "40", "40", "tall"]
+    paths = {}
+    for hp, wp, pat in EDT_CASES:
+        paths.setdefault(edt_column_path(hp), set()).add(pat)
+    assert set(paths) == {"8", "20", "40", "tall"}
+    for p in ("20", "40", "tall"):                        # every pattern on each of the paths the small tests never reach
+        assert {"corner", "sparse", "band"} <= paths[p], (p, paths[p])
+    sizes = {(hp, wp) for hp, wp, _ in EDT_CASES}
+    assert {(1280, 64), (1296, 64), (2560, 64), (2592, 64)} <= sizes and edt_column_path(1296) == "40" and edt_column_path(2592) == "tall"
+
+    from otvm_amd import lib as L
+    lib = L.load()
+    for hw, T in MR_SHAPES:
+        lau = mr_launches(T, hw)
+        assert int(lib.otvm_memory_read_f16x3_partial_count(T, hw)) == sum(l["chunks"] for l in lau), (hw, T)
+        for n in (1, T - 1):                              # the engine's two-step grouping sizes its workspace from these
+            if n:
+                assert int(lib.otvm_memory_read_f16x3_partial_count(n, hw)) == sum(l["chunks"] for l in mr_launches(n, hw))
+        assert all(l["chunk_tiles"] > 1 for l in lau), (hw, T, lau)
+        # 1080p with two slots cuts its 256 tiles into chunks of 64 that end exactly on the slot boundary (the next chunk
+        # starts a slot instead of wrapping into it); every other case has chunks that wrap
+        assert (lau[0]["crossing"] > 0) == ((hw, T) != (8160, 2)), (hw, T, lau)
+    assert sum(len(mr_launches(T, hw)) > 1 for hw, T in MR_SHAPES) >= 2
