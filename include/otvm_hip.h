@@ -40,7 +40,7 @@ extern "C" {
 #define OTVM_PREC_F16 2
 
 const char* otvm_last_error(void);
-#define OTVM_ABI_VERSION 20   /* 2: otvm_ppm_pool_ws_bytes(H, C); 3: otvm_conv_params.in_scale/in_shift/in_act;
+#define OTVM_ABI_VERSION 21   /* 2: otvm_ppm_pool_ws_bytes(H, C); 3: otvm_conv_params.in_scale/in_shift/in_act;
                                  4: otvm_conv_params.splitk_ws; 5: otvm_preprocess_params.fg_u8/bg_u8/u8_rgb;
                                  6: otvm_conv_params.tune + otvm_conv2d_candidates;
                                  7: folded GroupNorm tables on otvm_gn_apply's residual and otvm_upsample_bilinear's input;
@@ -60,7 +60,8 @@ const char* otvm_last_error(void);
                                  18: otvm_gram_params.diag / otvm_gn_predict_params.diag (conditioning + saturation diagnostics of the
                                      predicted statistics); implicit-GEMM tiles 32 + t with LDS-DMA weight stages and 64 + t = the same on
                                      v_mfma_f32_16x16x32_f16 (tune codes; no new entry points);
-                                 20: otvm_matting_grad_conn / _ws_bytes / _params (Grad and Conn matting metrics) */
+                                 20: otvm_matting_grad_conn / _ws_bytes / _params (Grad and Conn matting metrics);
+                                 21: otvm_optflow_farneback / _ws_bytes / _params, otvm_matting_messddt (MESSDdt) */
 int otvm_abi_version(void);
 
 /* ---------------------------------------------------------------- weights (load time) ----------
@@ -464,6 +465,24 @@ int64_t otvm_matting_grad_conn_ws_bytes(int H, int W);
  * levels[11] = t_k as float32, taps[18] = the L2-normalised 1-D Gaussian [9] and Gaussian-derivative [9] factors of hx.
  * Any pointer may be NULL.                                                                                           */
 int otvm_matting_grad_conn_params(int* cutoffs, float* levels, double* taps);
+/* Dense optical flow of two uint8 [H,W] frames: OpenCV's calcOpticalFlowFarneback(prev, next, None, 0.5, 5, 10, 2, 7, 1.5,
+ * OPTFLOW_FARNEBACK_GAUSSIAN), the reference's calcOpticalFlow (utils/tmp/metric.py:48-53).  flow: float [H,W,2] = (dx, dy).
+ * ws: otvm_optflow_farneback_ws_bytes(H, W) bytes of device memory, no initialisation; one ws serves one stream at a time.
+ * Any H in 1..65535 and W >= 1; deterministic (no atomics).                                                          */
+int otvm_optflow_farneback(const uint8_t* prev, const uint8_t* next, int H, int W, float* flow, void* ws, void* stream);
+int64_t otvm_optflow_farneback_ws_bytes(int H, int W);
+/* host-side constants for (H, W); returns the number of pyramid levels n (<= 6), in processing order (coarsest first):
+ * levels[4n] = (k, width, height, GaussianBlur ksize), blur_taps[79n] = each level's float32 kernel (zero padded),
+ * poly_taps[24] = g[0..7], xg[0..7], xxg[0..7] of FarnebackPolyExp(7, 1.5), poly_inv[4] = ig11, ig03, ig33, ig55,
+ * win_taps[6] = the 11-tap flow window kernel, centre first.  Any pointer may be NULL; -1 for H or W < 1.             */
+int otvm_optflow_farneback_params(int H, int W, int* levels, float* blur_taps, float* poly_taps, double* poly_inv, float* win_taps);
+/* MESSDdt of one pair of frames (metric.py:266-302): the flow of (t0, t1) as above, rounded half to even, and the
+ * reference's TRANSPOSED lookup -- pixel (r, c) of frame 1 is read at row clamp(c + dx, 0, H-1), column clamp(r + dy, 0, W-1).
+ * acc[2] (fp64, caller-zeroed) accumulates  sum |(p0-t0)^2 m0 - (p1w-t1w)^2 m1w|  (0..255 integers: error * 255^2, exact)
+ * and  sum m0.  Masks {0,1} or NULL (all pixels).  flow_out (optional, float [H,W,2]) receives the flow.
+ * ws: otvm_optflow_farneback_ws_bytes(H, W).                                                                         */
+int otvm_matting_messddt(const uint8_t* p0, const uint8_t* t0, const uint8_t* m0, const uint8_t* p1, const uint8_t* t1,
+                         const uint8_t* m1, int H, int W, double* acc, float* flow_out, void* ws, void* stream);
 
 /* ---------------------------------------------------------------- range guard / clear -----------
  * f16x3 splits fp32 operands into fp16 halves: |x| >= 65504 loses accuracy, >= 131008 becomes inf.

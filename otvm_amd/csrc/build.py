@@ -33,6 +33,7 @@ SOURCES = [
     ("memory_read_f16x3.hip", []),
     ("metrics.hip", []),
     ("metrics_grad_conn.hip", ["-ffp-contract=off"]),
+    ("optflow_farneback.hip", ["-ffp-contract=off"]),
     ("guard.hip", []),
     ("losses.hip", ["-ffp-contract=off"]),
 ]

@@ -188,7 +188,7 @@ def run_sharded(sequences, matte_fn, rank=0, world=1, device="cpu", reference_fn
     # err^2 / (mask_sum + 1); :252-264: dtSSD = per-pair sqrt(err^2) with its own normaliser), so the reduced report
     # carries the numbers the reference's BatchMetric would print, not only pooled ratios
     keys = ("frames", "sad_sum", "mse_num", "mask_sum", "dt_err2_sum", "dt_mask_sum", "mse_frame_sum", "dtssd_pair_sum", "dtssd_norm_sum",
-            "pairs", "img_frames", "grad_sum", "conn_sum", "ssda_frame_sum")
+            "pairs", "img_frames", "grad_sum", "conn_sum", "ssda_frame_sum", "fl_pairs", "messddt_pair_sum", "messddt_norm_sum")
     clip = [0.0] * len(keys)
     for out in outputs.values():
         m = out.get("metrics") if isinstance(out, dict) else None
@@ -204,7 +204,12 @@ def run_sharded(sequences, matte_fn, rank=0, world=1, device="cpu", reference_fn
             m["img_frames"] = float(m["frames"]) if img else 0.0
             m["grad_sum"], m["conn_sum"] = float(m.get("grad_sum", 0.0)), float(m.get("conn_sum", 0.0))
             m["ssda_frame_sum"] = float(sum(m.get("ssda_per_frame", [])))
-            clip = [c + float(m[k]) for c, k in zip(clip, keys)]
+            # MESSDdt (ClipMetrics(flow_metrics=True)): per-pair (error, num) as dtSSD; clips without it add nothing
+            fe, fn = m.get("messddt_per_pair", []), m.get("messddt_num_per_pair", [])
+            m["fl_pairs"] = float(len(fe)) if "messddt_per_pair" in m else 0.0
+            m["messddt_pair_sum"] = float(sum(fe))
+            m["messddt_norm_sum"] = float(sum(e / n for e, n in zip(fe, fn)))
+            clip =[c + float(m[k]) for c, k in zip(clip, keys)]
     red, (maxabs_g, wall_g) = reduce_metrics([sad, frames, secs] + clip, [maxabs, secs], device)
     sad_g, frames_g, secs_sum = red[:3]
     summary = dict(sad=sad_g, frames=frames_g, gpu_seconds=secs_sum, wall_seconds=wall_g, max_abs=maxabs_g,
@@ -230,4 +235,8 @@ def run_sharded(sequences, matte_fn, rank=0, world=1, device="cpu", reference_fn
             # per-frame means of BatchGradient / BatchConnectivity (no /1000) and of SSDA's error (metric.py:191-250)
             summary["gt_metrics"].update(grad_mean=g["grad_sum"] / g["img_frames"], conn_mean=g["conn_sum"] / g["img_frames"],
                                          ssda_mean=g["ssda_frame_sum"] / g["img_frames"])
+        if g["fl_pairs"] > 0:
+            # MESSDdt (metric.py:266-302): mean over pairs of the error and of error / num, as dtSSD above
+            summary["gt_metrics"].update(messddt_mean=g["messddt_pair_sum"] / g["fl_pairs"],
+                                         messddt_norm_mean=g["messddt_norm_sum"] / g["fl_pairs"])
     return summary

@@ -49,6 +49,8 @@ def main(argv=None):
                          "(dist.default_batch; measured +5 % / +41 % aggregate)")
     ap.add_argument("--all-metrics", action="store_true",
                     help="VideoMatting108: also Grad, Conn and SSDA against the ground truth (device kernels, metric.py:191-250)")
+    ap.add_argument("--messddt", action="store_true",
+                    help="VideoMatting108: also MESSDdt against the ground truth (Farneback flow on the device, metric.py:266-302)")
     ap.add_argument("--summary-json", default=None, help="rank 0 writes the reduced summary (frames, fps, metrics, shards) here")
     args = ap.parse_args(argv)
     from PIL import Image
@@ -169,7 +171,7 @@ def main(argv=None):
             res = run_video_matte(model, data["frames"], alphas=data["alphas"], backgrounds=data["backgrounds"],
                                   skip=args.skip, max_num=args.max_num, on_frame=save, device=dev,
                                   gt_alpha_u8=data["gt_alpha_u8"], gt_mask="unknown", keep_on_device=True,
-                                  gt_image_metrics=args.all_metrics)
+                                  gt_image_metrics=args.all_metrics, gt_flow_metrics=args.messddt)
         if writer is not None:
             writer.close()
         if args.viz:
@@ -195,7 +197,7 @@ def main(argv=None):
                                         backgrounds=[d["backgrounds"] for d in datas], skip=args.skip, max_num=args.max_num,
                                         on_frame=save, device=dev, keep_on_device=True,
                                         gt_alpha_u8=[d["gt_alpha_u8"] for d in datas], gt_mask="unknown",
-                                        gt_image_metrics=args.all_metrics)
+                                        gt_image_metrics=args.all_metrics, gt_flow_metrics=args.messddt)
         for w in writers:
             w.close()
         return res
@@ -228,6 +230,8 @@ def main(argv=None):
             extra = ""
             if "grad_mean" in g:
                 extra = " | Grad/frame %.4f | Conn/frame %.4f | SSDA/frame %.6f" % (g["grad_mean"], g["conn_mean"], g["ssda_mean"])
+            if "messddt_mean" in g:
+                extra += " | MESSDdt/pair %.6f" % g["messddt_mean"]
             print("vs ground truth (unknown band) | SAD/frame %.4f | MSE/frame %.6f (pooled %.6f) | dtSSD/pair %.6f%s | frames %d"
                   % (g["sad"], g["mse_mean"], g["mse"], g["dtssd_mean"], extra, g["frames"]))
     return summary

@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("OTVM_HIP_LIB") or os.path.join(_HERE, "libotvm_hip.so
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
 PREC_F32, PREC_F16X3, PREC_F16 = 0, 1, 2
-ABI_VERSION = 20         # include/otvm_hip.h OTVM_ABI_VERSION
+ABI_VERSION = 21        # include/otvm_hip.h OTVM_ABI_VERSION
 
 
 class ConvParams(C.Structure):
@@ -133,6 +133,10 @@ _PROTOS = {
     "otvm_matting_grad_conn": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp]),
     "otvm_matting_grad_conn_ws_bytes": (i64, [i32, i32]),
     "otvm_matting_grad_conn_params": (i32, [vp, vp, vp]),
+    "otvm_optflow_farneback": (i32, [vp, vp, i32, i32, vp, vp, vp]),
+    "otvm_optflow_farneback_ws_bytes": (i64, [i32, i32]),
+    "otvm_optflow_farneback_params": (i32, [i32, i32, vp, vp, vp, vp, vp]),
+    "otvm_matting_messddt": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
     "otvm_gn_stats_b": (i32, [vp, i64, i32, i32, vp, i32, i64, i32, vp]),
     "otvm_gn_table_b": (i32, [vp, i64, i32, vp, vp, vp, vp, i32, i32, i32, vp]),
     "otvm_gn_apply_b": (i32, [C.POINTER(GnApplyParams), vp]),

@@ -47,7 +47,7 @@ def _as_tensor(x):
 
 def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, skip=10, max_num=5,
                     frames_are_rgb=False, on_frame=None, device=None, keep_on_device=False, gt_alpha_u8=None,
-                    gt_mask_u8=None, gt_mask=None, gt_image_metrics=False):
+                    gt_mask_u8=None, gt_mask=None, gt_image_metrics=False, gt_flow_metrics=False):
     """Matte one sequence.
 
     model       : EvalModel (optionally wrapped in nn.DataParallel), on the GPU
@@ -58,7 +58,8 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
     gt_alpha_u8 : optional per-frame ground-truth alpha, uint8 [H,W]; with it SAD/MSE/dtSSD are accumulated on
                   the device (ClipMetrics) and returned under "metrics"; gt_mask_u8 = optional {0,1} evaluation masks,
                   gt_mask="unknown" = the reference metric's default mask (0 < gt < 255) instead; gt_image_metrics=True adds
-                  Grad, Conn and SSDA (ClipMetrics(image_metrics=True))
+                  Grad, Conn and SSDA (ClipMetrics(image_metrics=True)), gt_flow_metrics=True MESSDdt
+                  (ClipMetrics(flow_metrics=True))
     backgrounds : optional per-frame BG images (V108 composites fg*a + bg*(1-a)), same dtype / channel order as the
                   frames; default bg = fg
     Returns dict(alpha=[T,H,W] float32, alpha_u8=[T,H,W] uint8 (truncated, eval.py:209), trimap=[T,3,H,W],
@@ -69,7 +70,8 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
     dev = device or next(model.parameters()).device
     out_a, out_u8, out_t, bank_log = [], [], [], []
     core = model.module if hasattr(model, "module") else model
-    metrics = ClipMetrics(dev, image_metrics=gt_image_metrics) if gt_alpha_u8 is not None else None
+    metrics = (ClipMetrics(dev, image_metrics=gt_image_metrics, flow_metrics=gt_flow_metrics) if gt_alpha_u8 is not None
+               else None)
     # loop invariants: the user trimap (25 MB as fp32 at 1080p) is uploaded once, not once per frame; the dummy alpha
     # of the trimap flow is one tensor for the whole clip
     tri_dev = None
@@ -151,14 +153,14 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
 
 def run_video_matte_batch(model, clips, trimaps=None, alphas=None, backgrounds=None, skip=10, max_num=5, frames_are_rgb=False,
                           device=None, keep_on_device=False, on_frame=None, gt_alpha_u8=None, gt_mask=None,
-                          gt_image_metrics=False):
+                          gt_image_metrics=False, gt_flow_metrics=False):
     """Matte B sequences of one resolution in LOCK-STEP (round 3): frame i of every clip goes through the network in one
     batched step (EvalModel.forward_batch: one launch per layer over the B images, per-sequence memory banks).
     clips: list of B frame arrays ([T_b,H,W,3] uint8 / float, BGR unless frames_are_rgb); trimaps: list of B first-frame
     one-hot trimaps [3,H,W] (demo flow) or None with alphas = list of B per-frame GT alpha lists (V108 flow: the first-frame
     trimap is derived from the alpha); backgrounds: optional list of B per-frame background lists; gt_alpha_u8: optional
     list of B per-frame uint8 ground truths (SAD / MSE / dtSSD per clip, as run_video_matte; gt_image_metrics=True adds Grad,
-    Conn and SSDA); on_frame(b, i, alpha, u8, out).
+    Conn and SSDA, gt_flow_metrics=True MESSDdt); on_frame(b, i, alpha, u8, out).
     Clips may differ in LENGTH: the batch runs max(T_b) steps, a clip that has ended keeps feeding its last frame (its
     outputs from then on are discarded) -- sequences are independent (all recurrent state is per sequence), so
     this changes no result of the others; the frame flags follow the frame index, which the clips share.
@@ -175,7 +177,8 @@ def run_video_matte_batch(model, clips, trimaps=None, alphas=None, backgrounds=N
     core = model.module if hasattr(model, "module") else model
     dev = device or next(core.parameters()).device
     res = [dict(alpha=[], alpha_u8=[], trimap=[], bank_frames=[]) for _ in range(B)]
-    metrics = [ClipMetrics(dev, image_metrics=gt_image_metrics) for _ in range(B)] if gt_alpha_u8 is not None else None
+    metrics = ([ClipMetrics(dev, image_metrics=gt_image_metrics, flow_metrics=gt_flow_metrics) for _ in range(B)]
+               if gt_alpha_u8 is not None else None)
     tri_dev = None if trimaps is None else [_as_tensor(t).to(dev).float()[None, None] for t in trimaps]
     ones = None
     for i in range(T):
@@ -253,16 +256,22 @@ class ClipMetrics:
     explicit uint8 {0,1} masks.
     image_metrics=True also runs otvm_matting_grad_conn per frame into a second row buffer on the same stream: result()
     then adds Grad and Conn (BatchGradient / BatchConnectivity, metric.py:191-234, as they return them: no /1000) and SSDA
-    (metric.py:244-250: sqrt of the masked squared error / 255 and its count, from the SAD / MSE row)."""
+    (metric.py:244-250: sqrt of the masked squared error / 255 and its count, from the SAD / MSE row).
+    flow_metrics=True also runs otvm_matting_messddt on each pair (previous, current frame) into a third row buffer on the
+    same stream: result() then adds MESSDdt (metric.py:266-302: Farneback flow of the ground truth, the reference's
+    transposed lookup) per pair with its count, as dtSSD."""
 
-    def __init__(self, device, capacity=256, image_metrics=False):
+    def __init__(self, device, capacity=256, image_metrics=False, flow_metrics=False):
         from . import lib as L
         self.L, self.lib = L, L.load()
         self.device = device
         self.acc = torch.zeros(capacity, 5, dtype=torch.float64, device=device)
         self.image_metrics = bool(image_metrics)
         self.acc_gc = torch.zeros(capacity, 2, dtype=torch.float64, device=device) if self.image_metrics else None
+        self.flow_metrics = bool(flow_metrics)
+        self.acc_fl = torch.zeros(capacity, 2, dtype=torch.float64, device=device) if self.flow_metrics else None
         self.ws, self.ws_shape = None, None
+        self.ws_fl, self.ws_fl_shape = None, None
         self.prev = None
         self.frames = 0
 
@@ -279,6 +288,8 @@ class ClipMetrics:
             self.acc = torch.cat([self.acc, torch.zeros_like(self.acc)])
             if self.acc_gc is not None:
                 self.acc_gc = torch.cat([self.acc_gc, torch.zeros_like(self.acc_gc)])
+            if self.acc_fl is not None:
+                self.acc_fl = torch.cat([self.acc_fl, torch.zeros_like(self.acc_fl)])
         pp, tp, mp = self.prev if self.prev is not None else (None, None, None)
         ptr = lambda x: 0 if x is None else x.data_ptr()
         self.L.check(self.lib.otvm_matting_metrics(ptr(pred_u8), ptr(target_u8), ptr(mask_u8), ptr(pp), ptr(tp), ptr(mp),
@@ -291,6 +302,15 @@ class ClipMetrics:
             self.L.check(self.lib.otvm_matting_grad_conn(ptr(pred_u8), ptr(target_u8), ptr(mask_u8), H, W,
                                                          self.acc_gc[self.frames].data_ptr(), None, self.ws.data_ptr(), st),
                          "matting_grad_conn")
+        if self.flow_metrics and self.prev is not None:
+            H, W = pred_u8.shape[-2:]
+            if self.ws_fl_shape != (H, W):
+                self.ws_fl = torch.empty(self.lib.otvm_optflow_farneback_ws_bytes(H, W), dtype=torch.uint8, device=pred_u8.device)
+                self.ws_fl_shape = (H, W)
+            # row i > 0: the pair (i-1, i), flow of (target i-1, target i)
+            self.L.check(self.lib.otvm_matting_messddt(ptr(pp), ptr(tp), ptr(mp), ptr(pred_u8), ptr(target_u8), ptr(mask_u8), H, W,
+                                                       self.acc_fl[self.frames].data_ptr(), None, self.ws_fl.data_ptr(), st),
+                         "matting_messddt")
         self.prev = (pred_u8, target_u8, mask_u8)
         self.frames += 1
 
@@ -312,6 +332,10 @@ class ClipMetrics:
             res.update(grad_per_frame=gc[:, 0].tolist(), conn_per_frame=gc[:, 1].tolist(),
                        grad_sum=float(gc[:, 0].sum()), conn_sum=float(gc[:, 1].sum()),
                        ssda_per_frame=(rows[:, 1].sqrt() / 255.0).tolist(), ssda_num_per_frame=(rows[:, 2] + 1.0).tolist())
+        if self.flow_metrics:
+            fl = self.acc_fl[1:self.frames].cpu()
+            fe = (fl[:, 0] / 255.0 ** 2).tolist()
+            res.update(messddt_per_pair=fe, messddt_num_per_pair=(fl[:, 1] + 1.0).tolist(), messddt_sum=float(sum(fe)))
         return res
 
 

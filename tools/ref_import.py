@@ -27,6 +27,15 @@ def _make_cv2():
         assert distanceType == 2 and maskSize == 0
         return ndimage.distance_transform_edt(src != 0).astype(np.float32)
     m.distanceTransform = distanceTransform
+    m.OPTFLOW_FARNEBACK_GAUSSIAN = 256
+
+    def calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags):
+        # the restatement of tests/farneback_ref.py, for the reference's fixed arguments only (metric.py:48-53)
+        assert flow is None and (pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags) == (0.5, 5, 10, 2, 7, 1.5, 256)
+        sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+        from tests.farneback_ref import farneback
+        return farneback(prev, next, np.float32)
+    m.calcOpticalFlowFarneback = calcOpticalFlowFarneback
     return m
 
 
