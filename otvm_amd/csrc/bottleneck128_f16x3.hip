@@ -26,14 +26,8 @@
 // weights per workgroup for one 32-row MFMA tile (48 FLOP per weight byte: bound by the L2 -> CU path at ~50 % of the MFMA rate the
 // separate launches already reach) -- DESIGN.md 6.
 #include "common.h"
+#include "f16x3_ops.h"
 #include <hip/hip_fp16.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 #ifdef OTVM_BNK_TIMING
 // experiment build only (tools/bottleneck_bench.py --planes128): per-stage time of wave 0 of every workgroup, 100 MHz ticks
@@ -62,27 +56,6 @@ struct Bnk128Args {
 
 constexpr int PL = 128, CIN = 512, COUT = 512;
 constexpr int LDT = PL + 8;          // halfs per t1 / t2 row = 272 bytes (17 x 16: consecutive rows on distinct 16-byte slots)
-
-__device__ __forceinline__ void split4c(const f32x4 v, f16x4& hi, f16x4& lo) {
-    typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-    const fp16x2 p01 = __builtin_amdgcn_cvt_pkrtz(v.x, v.y);
-    const fp16x2 p23 = __builtin_amdgcn_cvt_pkrtz(v.z, v.w);
-    const f16x2 h01 = __builtin_bit_cast(f16x2, p01);
-    const f16x2 h23 = __builtin_bit_cast(f16x2, p23);
-    hi = f16x4{h01.x, h01.y, h23.x, h23.y};
-    lo = f16x4{(_Float16)(v.x - (float)h01.x), (_Float16)(v.y - (float)h01.y), (_Float16)(v.z - (float)h23.x),
-               (_Float16)(v.w - (float)h23.y)};
-}
-
-__device__ __forceinline__ void split1c(float v, _Float16& hi, _Float16& lo) {
-    hi = (_Float16)v;
-    lo = (_Float16)(v - (float)hi);
-}
-
-#define MFMA3X(ACC, AH, AL, BH, BL)                                             \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL, BH, ACC, 0, 0, 0);         \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH, BL, ACC, 0, 0, 0);         \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH, BH, ACC, 0, 0, 0)
 
 template <int TH, int TW, int NW>
 struct Bnk128Geom {
@@ -153,7 +126,7 @@ void stm_bottleneck128_f16x3_kernel(const Bnk128Args pa) {
             // (a value, not a load, is selected: outside rows carry EXACTLY 2^31 -- beyond the resource's range for every chunk)
             aoff[i] = ok ? ((unsigned)(iy * p.W + ix) * (unsigned)p.x_ld + (unsigned)ak) << 2 : 0x80000000u;
         }
-        __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
+        __amdgpu_buffer_rsrc_t x_rsrc = otvm_buffer_rsrc(p.x, p.x_bytes);
         // x runs TWO chunks ahead of the MFMAs (two register sets: 2 x 48 KiB in flight per CU -- every workgroup of the launch
         // streams x at the same time, the phase is bound by HBM / Infinity-Cache latency x bytes in flight).  W1: every wave needs
         // the fragments of ITS n-tiles only -- straight from L2 into registers, one chunk ahead, as in stages B and C (no weight
@@ -183,7 +156,7 @@ void stm_bottleneck128_f16x3_kernel(const Bnk128Args pa) {
 #pragma unroll
             for (int i = 0; i < NA; ++i) {
                 f16x4 hi, lo;
-                split4c(ra[i], hi, lo);
+                otvm_split4(ra[i], hi, lo);
                 *reinterpret_cast<f16x4*>(&Ah[(arow + AR * i) * LDA + ak]) = hi;
                 *reinterpret_cast<f16x4*>(&Al[(arow + AR * i) * LDA + ak]) = lo;
             }
@@ -272,7 +245,7 @@ void stm_bottleneck128_f16x3_kernel(const Bnk128Args pa) {
                     float v = acc[a][b][e] * sc + bi;
                     v = ok[e] ? (v > 0.f ? v : 0.f) : 0.f;
                     _Float16 h, l;
-                    split1c(v, h, l);
+                    otvm_split1(v, h, l);
                     T1h[o + ((e & 3) + 8 * (e >> 2)) * LDT] = h;
                     T1l[o + ((e & 3) + 8 * (e >> 2)) * LDT] = l;
                 }
@@ -398,7 +371,7 @@ void stm_bottleneck128_f16x3_kernel(const Bnk128Args pa) {
                 float v = acc2[a][b][e] * sc + bi;
                 v = v > 0.f ? v : 0.f;
                 _Float16 h, l;
-                split1c(v, h, l);
+                otvm_split1(v, h, l);
                 T2h[pr * LDT + n] = h;
                 T2l[pr * LDT + n] = l;
             }

@@ -22,13 +22,8 @@
 // accumulate; weights pre-split with a per-filter power-of-two scale (otvm_split_conv_weight_f16x3) and re-packed in MFMA
 // B-fragment order (otvm_pack_wave_weight_f16x3: [n/32][32-channel chunk][k-step][hi|lo][64 lanes][8 halfs]).
 #include "common.h"
+#include "f16x3_ops.h"
 #include <hip/hip_fp16.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 #ifdef OTVM_BNK_TIMING
 // experiment build only (tools/bottleneck_bench.py): per-stage time of wave 0 of every workgroup, 100 MHz ticks
@@ -60,27 +55,6 @@ constexpr int T1_HALFS = 352 * LDT;                                      // per 
 constexpr int STG_OFF = 2 * T1_HALFS;                                    // halfs: staging region behind the t1 planes
 constexpr int STG_HALFS = 9 * 2 * 2 * 512;                               // stage-B weights of one 16-channel stage (36 KiB)
 constexpr int LDS_BYTES = (STG_OFF + STG_HALFS) * 2;
-
-__device__ __forceinline__ void split4b(const f32x4 v, f16x4& hi, f16x4& lo) {
-    typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-    const fp16x2 p01 = __builtin_amdgcn_cvt_pkrtz(v.x, v.y);
-    const fp16x2 p23 = __builtin_amdgcn_cvt_pkrtz(v.z, v.w);
-    const f16x2 h01 = __builtin_bit_cast(f16x2, p01);
-    const f16x2 h23 = __builtin_bit_cast(f16x2, p23);
-    hi = f16x4{h01.x, h01.y, h23.x, h23.y};
-    lo = f16x4{(_Float16)(v.x - (float)h01.x), (_Float16)(v.y - (float)h01.y), (_Float16)(v.z - (float)h23.x),
-               (_Float16)(v.w - (float)h23.y)};
-}
-
-__device__ __forceinline__ void split1b(float v, _Float16& hi, _Float16& lo) {
-    hi = (_Float16)v;
-    lo = (_Float16)(v - (float)hi);
-}
-
-#define MFMA3(ACC, AH, AL, BH, BL)                                              \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL, BH, ACC, 0, 0, 0);         \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH, BL, ACC, 0, 0, 0);         \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH, BH, ACC, 0, 0, 0)
 
 template <bool FULL>
 __device__ __forceinline__ void store_patch(const float* patch, int prow, int pc, f32x4 sc4, f32x4 bi4, float* yp, int y, int tx0,
@@ -174,12 +148,12 @@ __global__ __launch_bounds__(256) void stm_bottleneck_f16x3_kernel(const BnkArgs
                 for (int t = 0; t < 3; ++t) {
                     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
                     f16x4 h0, l0, h1, l1;
-                    split4b(aok[t] ? ra[slot][t][2 * sk] : z, h0, l0);
-                    split4b(aok[t] ? ra[slot][t][2 * sk + 1] : z, h1, l1);
+                    otvm_split4(aok[t] ? ra[slot][t][2 * sk] : z, h0, l0);
+                    otvm_split4(aok[t] ? ra[slot][t][2 * sk + 1] : z, h1, l1);
                     const f16x8 ah = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
                     const f16x8 al = {l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w};
 #pragma unroll
-                    for (int b = 0; b < 2; ++b) { MFMA3(acc[t][b], ah, al, wb[slot][sk][b][0], wb[slot][sk][b][1]); }
+                    for (int b = 0; b < 2; ++b) { OTVM_MFMA3(acc[t][b], ah, al, wb[slot][sk][b][0], wb[slot][sk][b][1]); }
                 }
         }
         // t1 -> LDS (split); pixels outside the image are ZERO (the 3x3 conv's padding) -- only blocks on the image border
@@ -209,7 +183,7 @@ __global__ __launch_bounds__(256) void stm_bottleneck_f16x3_kernel(const BnkArgs
                     float v = acc[t][b][e] * sc + bi;
                     v = ok[e] ? (v > 0.f ? v : 0.f) : 0.f;
                     _Float16 h, l;
-                    split1b(v, h, l);
+                    otvm_split1(v, h, l);
                     T1h[o + ((e & 3) + 8 * (e >> 2)) * LDT] = h;
                     T1l[o + ((e & 3) + 8 * (e >> 2)) * LDT] = l;
                 }
@@ -335,7 +309,7 @@ __global__ __launch_bounds__(256) void stm_bottleneck_f16x3_kernel(const BnkArgs
                 float v = acc2[a][b][e] * sc + bi;
                 v = v > 0.f ? v : 0.f;
                 _Float16 h, l;
-                split1b(v, h, l);
+                otvm_split1(v, h, l);
                 T2h[pr * LDT + n] = h;
                 T2l[pr * LDT + n] = l;
             }
@@ -365,8 +339,8 @@ __global__ __launch_bounds__(256) void stm_bottleneck_f16x3_kernel(const BnkArgs
             for (int ks = 0; ks < 4; ++ks) {
                 const f32x4 z = {0.f, 0.f, 0.f, 0.f};
                 f16x4 h0, l0, h1, l1;
-                split4b(ok ? v[ks][0] : z, h0, l0);
-                split4b(ok ? v[ks][1] : z, h1, l1);
+                otvm_split4(ok ? v[ks][0] : z, h0, l0);
+                otvm_split4(ok ? v[ks][1] : z, h1, l1);
                 xh[a][ks] = f16x8{h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
                 xl[a][ks] = f16x8{l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w};
             }

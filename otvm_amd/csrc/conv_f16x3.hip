@@ -155,8 +155,8 @@ __global__ __launch_bounds__(64) void conv_wave_f16x3_kernel(const Conv3Args pa)
                 v0 = ok ? v0 : z;
                 v1 = ok ? v1 : z;
                 f16x4 h0, l0, h1, l1;
-                split4(v0, h0, l0);
-                split4(v1, h1, l1);
+                otvm_split4(v0, h0, l0);
+                otvm_split4(v1, h1, l1);
                 ah[a] = f16x8{h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
                 al[a] = f16x8{l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w};
             }
@@ -412,25 +412,8 @@ int otvm_conv2d_patch_f16x3_impl(const otvm_conv_params* p, void* stream);    //
 // tile shared by S workgroups (S > 1: partial tiles through the caller's workspace, added in a fixed order by
 // splitk_finish_kernel), or the 3x3 patch kernel.  otvm_conv_params.tune forces one (the host's plan-time autotuner,
 // otvm_amd/engine.py, times the candidates of otvm_conv2d_candidates on the device); 0 = the heuristic below.
-enum { T256x256 = 0, T256x128, T128x128, T128x64, T64x64, T256x64, T256x32, T256x128W4, T128x256W4, T64x64W1, T64x64D, T128x64D,
-       T_STEM = 12, T256x256W4 = 13, T_PATCH = 14, T_COUNT = 15,
-       // round 5: tile t with LDS-DMA weight stages = T_GLDS + t (conv_f16x3_glds.hip; see the kernel's GLDS comment)
-       T_GLDS = 32,
-       // ... and T_M16 + t: the LDS-DMA tile t multiplying with v_mfma_f32_16x16x32_f16 (conv_f16x3_m16.hip; the kernel's M16 comment)
-       T_M16 = 64 };
+// The tiles, their ids and their forms: IGEMM_TILES in conv_f16x3_kernel.h.
 static inline int tune_code(int tile, int S) { return (tile + 1) * 16 + S; }
-static inline bool is_m16_tile(int t) { return t >= T_M16 && t < T_M16 + T_STEM; }
-static inline bool is_glds_tile(int t) {                    // (either matrix-core form)
-    const int b = t - (is_m16_tile(t) ? T_M16 : T_GLDS);
-    return b == T256x256 || b == T256x128 || b == T128x128 || b == T128x64 || b == T64x64 || b == T256x64 || b == T256x32 ||
-           b == T256x128W4 || b == T128x256W4 || b == T64x64D || b == T128x64D;
-}
-static inline bool is_gemm_tile(int t) { return (t >= 0 && t < T_STEM) || t == T256x256W4 || is_glds_tile(t); }
-static inline int base_tile(int t) { return is_glds_tile(t) ? t - (is_m16_tile(t) ? T_M16 : T_GLDS) : t; }
-static const int TILE_BM_[T_COUNT] = {256, 256, 128, 128, 64, 256, 256, 256, 128, 64, 64, 128, 0, 256, 0};
-static const int TILE_BN_[T_COUNT] = {256, 128, 128, 64, 64, 64, 32, 128, 256, 64, 64, 64, 0, 256, 0};
-static inline int TILE_BM(int t) { return TILE_BM_[base_tile(t)]; }
-static inline int TILE_BN(int t) { return TILE_BN_[base_tile(t)]; }
 
 static int launch_wave(Conv3Args& a, hipStream_t s, int ksplit) {
     a.tiles_m = otvm_ceil_div(a.M, 64);
@@ -448,34 +431,10 @@ static int launch_wave(Conv3Args& a, hipStream_t s, int ksplit) {
 
 static int launch_tile(int tile, Conv3Args& a, hipStream_t s, int S) {
     if (a.npass == 1) return otvm_launch_tile_p1(tile, a, s, S);       // precision "f16": conv_f16x3_p1.hip / _p1g.hip
-    switch (tile) {
-        case T256x256: return launch3<256, 256, 4, 2>(a, s, S);
-        case T256x128: return launch3<256, 128, 4, 2>(a, s, S);
-        case T128x128: return launch3<128, 128, 2, 2>(a, s, S);
-        case T128x64: return launch3<128, 64, 2, 2>(a, s, S);
-        case T64x64: return launch3<64, 64, 2, 2>(a, s, S);
-        case T256x64: return launch3<256, 64, 4, 1>(a, s, S);
-        case T256x32: return launch3<256, 32, 4, 1>(a, s, S);
-        // 4-wave workgroups with a single LDS stage (61 KB): two per CU, so one workgroup's epilogue (output stores,
-        // GroupNorm sums) overlaps the other's main loop -- candidates for the short-K, output-heavy 1x1 layers
-        case T256x128W4: return launch3<256, 128, 2, 2, false, true>(a, s, S);
-        case T128x256W4: return launch3<128, 256, 2, 2, false, true>(a, s, S);
-        // one-wave workgroups, operands straight from L2 into MFMA registers (small maps)
-        case T64x64W1: return launch_wave(a, s, S);
-        // pipelined small tiles: two LDS stages, one barrier per chunk, the next chunk converted under the MFMAs
-        case T64x64D: return launch3<64, 64, 2, 2, true>(a, s, S);
-        case T128x64D: return launch3<128, 64, 2, 2, true>(a, s, S);
-        // 256x256 with FOUR waves: every wave owns 128x128 (4x4 accumulator tiles, 256 registers), one wave per SIMD.  Per
-        // 16-deep k-step a wave reads 16 fragments for 48 MFMAs, the 8-wave tile 12 for 24: a third less LDS traffic per
-        // MFMA (tools/probes/lds_probe.hip: ~13 clocks per wave-wide b128 access with four waves issuing, so the 8-wave
-        // tile's fragment reads take about as long as its MFMAs).  Measured: 256->256 3x3 at 272x480 0.462 vs 0.479 ms, but
-        // 512->512 0.445 vs 0.408, 2048->256 1.45 vs 1.15, the 1x1 layers 20-40 % slower -- a single wave per SIMD has
-        // nothing to overlap its own fragment reads with.  Kept as a forced configuration (tune code 225), not a candidate.
-        case T256x256W4: return launch3<256, 256, 2, 2, false, true>(a, s, S);
-    }
-    if (is_glds_tile(tile)) return is_m16_tile(tile) ? otvm_launch_m16_tile(tile - T_M16, a, s, S) : otvm_launch_glds_tile(tile - T_GLDS, a, s, S);
-    otvm_set_error("otvm_conv2d(f16x3): unknown tile %d", tile);
-    return 1;
+    if (tile == T64x64W1) return launch_wave(a, s, S);
+    if (is_m16_tile(tile)) return otvm_launch_m16_tile(tile - T_M16, a, s, S);
+    if (is_glds_tile(tile)) return otvm_launch_glds_tile(tile - T_GLDS, a, s, S);
+    return launch_tile_form<false, 3, false>(tile, a, s, S);
 }
 
 // is (tile, S) a legal configuration of this layer?

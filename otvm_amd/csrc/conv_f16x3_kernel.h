@@ -1,11 +1,12 @@
-// The implicit-GEMM f16x3 kernel template and its launcher (internal header of conv_f16x3.hip and conv_f16x3_glds.hip: the
-// register-staged tiles are instantiated in the first translation unit, the LDS-DMA ("G") tiles in the second, so the two
-// compile side by side).
+// The implicit-GEMM f16x3 kernel template, its launcher and the tile table (internal header of conv_f16x3.hip and of the four
+// translation units that instantiate one FORM of the tiles each -- conv_f16x3_glds.hip, _m16.hip, _p1.hip, _p1g.hip -- so that the
+// five sets of instantiations compile side by side).
 #pragma once
 // (the LDS-DMA instructions are issued from inline asm that writes M0, a register the compiler reserves: it re-materialises M0 in
 //  front of every use of its own, so the clobber is harmless, but clang warns about any reserved register in a clobber list)
 #pragma clang diagnostic ignored "-Winline-asm"
 #include "common.h"
+#include "f16x3_ops.h"
 #include <type_traits>
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
@@ -43,11 +44,6 @@
 #define OTVM_BRANCHY_LOADS 1
 #endif
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 struct Conv3Args {
     const float* in; const _Float16* wh; const _Float16* wl; const float* wscale; const float* bias;
@@ -77,12 +73,12 @@ struct Conv3Args {
     int npass;                   // 3 = f16x3, 1 = precision "f16" (one MFMA pass on fp16-rounded operands; conv_f16x3_p1.hip)
 };
 
-// conv_f16x3_glds.hip: the LDS-DMA form of implicit-GEMM tile `base` (the enum of conv_f16x3.hip), K split over S workgroups
-int otvm_launch_glds_tile(int base, Conv3Args& a, hipStream_t s, int S);
-// conv_f16x3_m16.hip: the LDS-DMA tile `base` on v_mfma_f32_16x16x32_f16 (M16)
-int otvm_launch_m16_tile(int base, Conv3Args& a, hipStream_t s, int S);
-// conv_f16x3_p1.hip: the single-pass ("f16") form of tile `tile` (register-staged t or LDS-DMA 32 + t)
-int otvm_launch_tile_p1(int tile, Conv3Args& a, hipStream_t s, int S);
+// One form of implicit-GEMM tile `base` (an id of IGEMM_TILES below), K split over S workgroups; each is defined in the translation
+// unit that instantiates the form:
+int otvm_launch_glds_tile(int base, Conv3Args& a, hipStream_t s, int S);      // conv_f16x3_glds.hip: LDS-DMA weight stages
+int otvm_launch_m16_tile(int base, Conv3Args& a, hipStream_t s, int S);       // conv_f16x3_m16.hip: LDS-DMA on v_mfma_f32_16x16x32_f16
+int otvm_launch_tile_p1(int tile, Conv3Args& a, hipStream_t s, int S);        // conv_f16x3_p1.hip: single pass, staged t or T_GLDS + t
+int otvm_launch_glds_tile_p1(int base, Conv3Args& a, hipStream_t s, int S);   // conv_f16x3_p1g.hip: single pass, LDS-DMA
 
 namespace {
 
@@ -90,18 +86,6 @@ constexpr int BK = 32;
 constexpr int LDH = 40;          // halfs per LDS row (32 + 8 pad) = 80 bytes
 
 inline bool f16x3_fast_layout(int taps, int I_pad) { return I_pad % 32 == 0 && taps <= 32; }
-
-__device__ __forceinline__ void split4(const f32x4 v, f16x4& hi, f16x4& lo) {
-    // hi: round-toward-zero pack (any rounding works, lo is computed exactly against it)
-    typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-    const fp16x2 p01 = __builtin_amdgcn_cvt_pkrtz(v.x, v.y);
-    const fp16x2 p23 = __builtin_amdgcn_cvt_pkrtz(v.z, v.w);
-    const f16x2 h01 = __builtin_bit_cast(f16x2, p01);
-    const f16x2 h23 = __builtin_bit_cast(f16x2, p23);
-    hi = f16x4{h01.x, h01.y, h23.x, h23.y};
-    lo = f16x4{(_Float16)(v.x - (float)h01.x), (_Float16)(v.y - (float)h01.y), (_Float16)(v.z - (float)h23.x),
-               (_Float16)(v.w - (float)h23.y)};
-}
 
 // FAST: Cin % 32 == 0 and <= 32 taps -> a K chunk never straddles a tap, so the tap walk is wave-uniform
 // (scalar registers) and the per-row work per chunk shrinks to one add and one mask test.
@@ -229,7 +213,7 @@ void conv_igemm_f16x3_kernel(const Conv3Args pa) {
     const int g0 = wave * NBL;
     const _Float16* const dma_src = GLDS ? p.wf + ((int64_t)((n0 >> 5) + (g0 >> 2)) * p.nchunks) * 2048 + (g0 & 3) * 512 + lane * 8 : nullptr;
     const unsigned dma_dst = GLDS ? __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + STAGE_A + g0 * 512)) : 0u;
-    __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, GLDS ? p.in_bytes : 0, 0x00020000);
+    __amdgpu_buffer_rsrc_t in_rsrc = otvm_buffer_rsrc(p.in, GLDS ? p.in_bytes : 0);
     // chunk c's blocks -> stage `buf`.  The immediate offset of an LDS-DMA instruction moves BOTH addresses, and the blocks are
     // consecutive on both sides.  (s_nop: one wait state between the SALU write of M0 and its use)
     auto dma_b = [&](int c, int buf) __attribute__((always_inline)) {
@@ -333,7 +317,6 @@ void conv_igemm_f16x3_kernel(const Conv3Args pa) {
                     // branch-free AND traffic-free for padding lanes: an offset beyond the resource's size returns zeros
                     // (pure arithmetic on purpose: a select between the two offsets comes back from the compiler as an if / else
                     //  around two loads, i.e. one or two load instructions per row depending on the wave's lanes)
-                    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
                     const unsigned okb = (tapmask[i] >> u_tap) & 1u;
                     const unsigned boff = ((unsigned)(rowoff[i] + delta) << 2) | ((okb ^ 1u) << 31);
                     ra[i] = __builtin_bit_cast(f32x4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(in_rsrc, boff, 0, 0));
@@ -405,7 +388,7 @@ void conv_igemm_f16x3_kernel(const Conv3Args pa) {
             const f32x4 z = {0.f, 0.f, 0.f, 0.f};
             if (!GLDS || NORM_IN) v = (okmask >> i) & 1u ? v : z;      // (GLDS: a padding lane was loaded as zeros; the normalisation moves them)
             if constexpr (NPASS == 3) {
-                split4(v, hi, lo);
+                otvm_split4(v, hi, lo);
                 // M16: k-octet o of row r sits at octet o ^ f(r), f = bit 2 ^ bit 3 of r: with the plain layout the 16x16x32
                 // A fragment (row lane & 15, octet lane >> 4, 80-byte rows) is a 2-way bank conflict in every lane group
                 const int row = arow + A_ROWS * i;
@@ -970,6 +953,90 @@ int launch3(Conv3Args& a, hipStream_t s, int ksplit = 1) {
     }
     OTVM_CHECK_LAUNCH("otvm_conv2d(f16x3)");
     return 0;
+}
+
+// ---- the tile table: every implicit-GEMM tile exists HERE and nowhere else.  The ids are part of every tune code (tune_code() in
+// conv_f16x3.hip), of the engine's tune files and of profiles/*_autotune_*.json: a new tile gets a new number, no number is reused.
+// tools/conv_bench.py prints tile names from a `names` dict of its own, which must follow this table.
+// Ids outside it: T_STEM (conv_stem_f16x3.hip) and T_PATCH (conv_patch_f16x3.hip); T_GLDS + t / T_M16 + t name a FORM of tile t.
+enum { T256x256 = 0, T256x128, T128x128, T128x64, T64x64, T256x64, T256x32, T256x128W4, T128x256W4, T64x64W1, T64x64D, T128x64D,
+       T_STEM = 12, T256x256W4 = 13, T_PATCH = 14,
+       T_GLDS = 32,        // round 5: tile t with LDS-DMA weight stages (see the kernel's GLDS comment)
+       T_M16 = 64 };       // ... and the LDS-DMA tile t multiplying with v_mfma_f32_16x16x32_f16 (the kernel's M16 comment)
+// the forms of the kernel template a tile is instantiated in, one translation unit each
+enum : unsigned { F_STAGED = 1,        // register-staged weights, f16x3 (conv_f16x3.hip)
+                  F_STAGED_P1 = 2,     // ... single pass, precision "f16" (conv_f16x3_p1.hip)
+                  F_GLDS = 4,          // LDS-DMA weight stages (conv_f16x3_glds.hip)
+                  F_GLDS_P1 = 8,       // ... single pass (conv_f16x3_p1g.hip)
+                  F_M16 = 16,          // LDS-DMA on the 16x16x32 instruction (conv_f16x3_m16.hip)
+                  F_ALL = 31 };
+struct IgemmTile {
+    int id, BM, BN, WM, WN;    // BM x BN outputs per workgroup, WM x WN waves
+    bool DB;                   // the pipelined two-stage loop on a small tile
+    bool FAST_ONLY;            // the staged forms take whole-chunk layers only (no generic-decode kernels; every LDS-DMA form is)
+    unsigned forms;
+};
+constexpr IgemmTile IGEMM_TILES[] = {
+    {T256x256, 256, 256, 4, 2, false, false, F_ALL},
+    {T256x128, 256, 128, 4, 2, false, false, F_ALL},
+    {T128x128, 128, 128, 2, 2, false, false, F_ALL},
+    {T128x64, 128, 64, 2, 2, false, false, F_ALL},
+    {T64x64, 64, 64, 2, 2, false, false, F_ALL},
+    {T256x64, 256, 64, 4, 1, false, false, F_ALL},
+    {T256x32, 256, 32, 4, 1, false, false, F_ALL},
+    // 4-wave workgroups with a single LDS stage (61 KB): two per CU, so one workgroup's epilogue (output stores,
+    // GroupNorm sums) overlaps the other's main loop -- candidates for the short-K, output-heavy 1x1 layers
+    {T256x128W4, 256, 128, 2, 2, false, true, F_ALL},
+    {T128x256W4, 128, 256, 2, 2, false, true, F_ALL},
+    // one-wave workgroups, operands straight from L2 into MFMA registers (small maps): conv_wave_f16x3_kernel of conv_f16x3.hip,
+    // no form of this template
+    {T64x64W1, 64, 64, 1, 1, false, true, 0},
+    // pipelined small tiles: two LDS stages, one barrier per chunk, the next chunk converted under the MFMAs
+    {T64x64D, 64, 64, 2, 2, true, false, F_ALL},
+    {T128x64D, 128, 64, 2, 2, true, false, F_ALL},
+    // 256x256 with FOUR waves: every wave owns 128x128 (4x4 accumulator tiles, 256 registers), one wave per SIMD.  Per
+    // 16-deep k-step a wave reads 16 fragments for 48 MFMAs, the 8-wave tile 12 for 24: a third less LDS traffic per
+    // MFMA (tools/probes/lds_probe.hip: ~13 clocks per wave-wide b128 access with four waves issuing, so the 8-wave
+    // tile's fragment reads take about as long as its MFMAs).  Measured: 256->256 3x3 at 272x480 0.462 vs 0.479 ms, but
+    // 512->512 0.445 vs 0.408, 2048->256 1.45 vs 1.15, the 1x1 layers 20-40 % slower -- a single wave per SIMD has
+    // nothing to overlap its own fragment reads with.  Kept as a forced configuration (tune code 225), not a candidate.
+    {T256x256W4, 256, 256, 2, 2, false, true, F_STAGED},
+};
+constexpr int N_IGEMM_TILES = sizeof(IGEMM_TILES) / sizeof(IGEMM_TILES[0]);
+
+inline const IgemmTile* find_tile(int id) {
+    for (const IgemmTile& r : IGEMM_TILES)
+        if (r.id == id) return &r;
+    return nullptr;
+}
+inline bool tile_has(int id, unsigned forms) {
+    const IgemmTile* r = find_tile(id);
+    return r && (r->forms & forms) != 0;
+}
+inline bool is_m16_tile(int t) { return tile_has(t - T_M16, F_M16); }
+inline bool is_glds_tile(int t) { return is_m16_tile(t) || tile_has(t - T_GLDS, F_GLDS); }      // (either matrix-core form)
+inline int base_tile(int t) { return is_m16_tile(t) ? t - T_M16 : (is_glds_tile(t) ? t - T_GLDS : t); }
+inline bool is_gemm_tile(int t) { return find_tile(base_tile(t)) != nullptr; }
+inline int TILE_BM(int t) { return find_tile(base_tile(t))->BM; }                               // (t: an is_gemm_tile())
+inline int TILE_BN(int t) { return find_tile(base_tile(t))->BN; }
+
+constexpr unsigned tile_form(bool GLDS, int NPASS, bool M16) {
+    return M16 ? F_M16 : (GLDS ? (NPASS == 1 ? F_GLDS_P1 : F_GLDS) : (NPASS == 1 ? F_STAGED_P1 : F_STAGED));
+}
+// launch tile `id` in the form (GLDS, NPASS, M16): instantiates the kernels of exactly the table rows that have the form
+template <bool GLDS, int NPASS, bool M16, int I = 0>
+int launch_tile_form(int id, Conv3Args& a, hipStream_t s, int S) {
+    if constexpr (I < N_IGEMM_TILES) {
+        constexpr IgemmTile r = IGEMM_TILES[I];
+        if constexpr ((r.forms & tile_form(GLDS, NPASS, M16)) != 0) {
+            if (id == r.id) return launch3<r.BM, r.BN, r.WM, r.WN, r.DB, GLDS || r.FAST_ONLY, GLDS, NPASS, M16>(a, s, S);
+        }
+        return launch_tile_form<GLDS, NPASS, M16, I + 1>(id, a, s, S);
+    } else {
+        otvm_set_error("otvm_conv2d(%s): tile %d has no %s form", NPASS == 1 ? "f16" : "f16x3", id,
+                       M16 ? "16x16x32" : (GLDS ? "LDS-DMA" : "register-staged"));
+        return 1;
+    }
 }
 
 }  // namespace

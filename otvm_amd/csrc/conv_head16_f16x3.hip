@@ -15,11 +15,7 @@
 //     scale, bias, LeakyReLU, the hidden state (optional), then the head on 16 registers.
 #include "common.h"
 #include "head_math.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+#include "f16x3_ops.h"
 
 namespace {
 
@@ -35,17 +31,6 @@ struct Head16Args {
 constexpr int TH = 8, TW = 32, PH = TH + 2, PW = TW + 2, NPIX = PH * PW;
 constexpr int LDP = 40;                  // halfs per patch pixel: 32 channels + 8 pad = 80 bytes
 constexpr int EPL = 20;                  // floats per epilogue row: 16 channels + 4 pad
-
-__device__ __forceinline__ void split4h(const f32x4 v, f16x4& hi, f16x4& lo) {
-    typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-    const fp16x2 p01 = __builtin_amdgcn_cvt_pkrtz(v.x, v.y);
-    const fp16x2 p23 = __builtin_amdgcn_cvt_pkrtz(v.z, v.w);
-    const f16x2 h01 = __builtin_bit_cast(f16x2, p01);
-    const f16x2 h23 = __builtin_bit_cast(f16x2, p23);
-    hi = f16x4{h01.x, h01.y, h23.x, h23.y};
-    lo = f16x4{(_Float16)(v.x - (float)h01.x), (_Float16)(v.y - (float)h01.y), (_Float16)(v.z - (float)h23.x),
-               (_Float16)(v.w - (float)h23.y)};
-}
 
 // timing probes for tools/build_variant.sh (the results are WRONG with any of them set): which part of the kernel costs what
 #ifndef OTVM_H16_NOPATCH
@@ -112,8 +97,7 @@ __global__ __launch_bounds__(256, OTVM_HEAD16_WGS) void conv_head16_f16x3_kernel
     // ---- the input patch: 10 x 34 pixels x 32 channels, loaded and split once (zero outside the image: the conv's padding)
     constexpr int NP = (NPIX * 8 + 255) / 256;
     // (round 5: buffer loads without a branch -- a pixel outside the image carries an out-of-range offset and reads zeros)
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000);
+    __amdgpu_buffer_rsrc_t in_rsrc = otvm_buffer_rsrc(p.in, p.in_bytes);
     f32x4 rp[NP];
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
@@ -134,7 +118,7 @@ __global__ __launch_bounds__(256, OTVM_HEAD16_WGS) void conv_head16_f16x3_kernel
         const int idx = tid + k * 256;
         if (idx < NPIX * 8) {
             f16x4 hi, lo;
-            split4h(rp[k], hi, lo);
+            otvm_split4(rp[k], hi, lo);
             const int pix = idx >> 3, c4 = (idx & 7) * 4;
             *reinterpret_cast<f16x4*>(&Ph[pix * LDP + c4]) = hi;
             *reinterpret_cast<f16x4*>(&Pl[pix * LDP + c4]) = lo;

@@ -12,9 +12,7 @@
 // K ordering inside a 8-wide group is permuted (lane half h supplies k = 8j+4h+i at MFMA step i) --
 // identically for A and B, so the contraction is unchanged while every LDS read is a b128.
 #include "common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "f16x3_ops.h"
 
 namespace {
 

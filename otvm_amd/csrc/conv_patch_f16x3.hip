@@ -17,14 +17,9 @@
 #pragma clang diagnostic ignored "-Winline-asm"      // (M0 in an asm clobber list: see conv_f16x3_kernel.h)
 #include "common.h"
 #include "head_math.h"
+#include "f16x3_ops.h"
 #include <type_traits>
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 // timing probes for tools/build_variant.sh (results are WRONG with any of them set)
 #ifndef OTVM_PABL_NOMFMA
@@ -80,17 +75,6 @@ struct PatchArgs {
 
 constexpr int CB = 16;           // channels per stage = one MFMA k-step
 constexpr int LDP = 24;          // halfs per patch pixel (16 channels + 8 pad) = 48 bytes: 3r mod 16 distinct -> conflict-free b128
-
-__device__ __forceinline__ void split4p(const f32x4 v, f16x4& hi, f16x4& lo) {
-    typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-    const fp16x2 p01 = __builtin_amdgcn_cvt_pkrtz(v.x, v.y);
-    const fp16x2 p23 = __builtin_amdgcn_cvt_pkrtz(v.z, v.w);
-    const f16x2 h01 = __builtin_bit_cast(f16x2, p01);
-    const f16x2 h23 = __builtin_bit_cast(f16x2, p23);
-    hi = f16x4{h01.x, h01.y, h23.x, h23.y};
-    lo = f16x4{(_Float16)(v.x - (float)h01.x), (_Float16)(v.y - (float)h01.y), (_Float16)(v.z - (float)h23.x),
-               (_Float16)(v.w - (float)h23.y)};
-}
 
 #if OTVM_PABL_MFMA16
 __device__ __forceinline__ f32x16 mfma_probe16(const f16x8 a, const f16x8 b, f32x16 c) {
@@ -215,9 +199,8 @@ void conv_patch_f16x3_kernel(const PatchArgs pa) {
     // round 5: the patch is loaded through buffer resources, without a branch: a pixel outside the image carries an offset
     // beyond the resource's range and the hardware returns zeros (the `if (inside) load` form was an exec-masked branch per
     // load, i.e. NP extra basic blocks in the K loop)
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t res_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(INRES ? p.in_res : p.in), 0, INRES ? p.in_res_bytes : 0, 0x00020000);
+    __amdgpu_buffer_rsrc_t in_rsrc = otvm_buffer_rsrc(p.in, p.in_bytes);
+    __amdgpu_buffer_rsrc_t res_rsrc = otvm_buffer_rsrc(INRES ? p.in_res : p.in, INRES ? p.in_res_bytes : 0);
     // ---- round 6: lean staging of the nine-tap 16x16x32 tiles (LEAN).  The generic staging below recomputes, per stage and per
     // element, everything that does not depend on the stage -- patch coordinates (a division by PW), the image test, the LDS
     // address, the weight piece's place -- and tests its run-time switches (in_scale, in_relu, in_act) per element: ~1200 non-MFMA
@@ -338,7 +321,7 @@ void conv_patch_f16x3_kernel(const PatchArgs pa) {
             for (int k = 0; k < NP; ++k) {
                 if (k + 1 < NP || tid + k * NT < NPIX * 4) {            // (only the last element of a thread can lie behind the patch)
                     f16x4 hi, lo;
-                    split4p(rp[k], hi, lo);
+                    otvm_split4(rp[k], hi, lo);
                     *reinterpret_cast<f16x4*>(&Ph[l_o0 + 512 * k]) = hi;
                     *reinterpret_cast<f16x4*>(&Pl[l_o0 + 512 * k]) = lo;
                 }
@@ -377,12 +360,12 @@ void conv_patch_f16x3_kernel(const PatchArgs pa) {
                     f16x4 hi, lo;
                     const int pix = idx >> 2, c4 = (idx & 3) * 4;
                     if constexpr (M16) {
-                        split4p(v, hi, lo);
+                        otvm_split4(v, hi, lo);
                         const int o = (((idx >> 1) & 1) * PLANE + pix) * 8 + (idx & 1) * 4;     // [octet][pixel][8 halfs]
                         *reinterpret_cast<f16x4*>(&Ph[o]) = hi;
                         *reinterpret_cast<f16x4*>(&Pl[o]) = lo;
                     } else if constexpr (NPASS == 3) {
-                        split4p(v, hi, lo);
+                        otvm_split4(v, hi, lo);
                         *reinterpret_cast<f16x4*>(&Ph[pix * LDP + c4]) = hi;
                         *reinterpret_cast<f16x4*>(&Pl[pix * LDP + c4]) = lo;
                     } else {

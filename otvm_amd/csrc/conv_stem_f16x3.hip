@@ -13,14 +13,9 @@
 // straight into registers, one k-step ahead.  Epilogue as conv_patch_f16x3.hip (scale, bias, activation, optional fused
 // GroupNorm statistics).
 #include "common.h"
+#include "f16x3_ops.h"
 #include <type_traits>
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -36,17 +31,6 @@ constexpr int TH = 8, TW = 32, NW = 4, NT = NW * 64;
 constexpr int TM = TH / NW, TN = 2;                        // 2 output rows x 64 channels per wave
 constexpr int PH = 2 * TH + 5, PW = 2 * TW + 5, NPIX = PH * PW;          // 21 x 69 input pixels
 constexpr int KSTEPS = 25;                                                // 49 taps, two per k-step
-
-__device__ __forceinline__ void split4s(const f32x4 v, f16x4& hi, f16x4& lo) {
-    typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-    const fp16x2 p01 = __builtin_amdgcn_cvt_pkrtz(v.x, v.y);
-    const fp16x2 p23 = __builtin_amdgcn_cvt_pkrtz(v.z, v.w);
-    const f16x2 h01 = __builtin_bit_cast(f16x2, p01);
-    const f16x2 h23 = __builtin_bit_cast(f16x2, p23);
-    hi = f16x4{h01.x, h01.y, h23.x, h23.y};
-    lo = f16x4{(_Float16)(v.x - (float)h01.x), (_Float16)(v.y - (float)h01.y), (_Float16)(v.z - (float)h23.x),
-               (_Float16)(v.w - (float)h23.y)};
-}
 
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_stem_f16x3_kernel(const StemArgs pa) {
     StemArgs p = pa;
@@ -96,7 +80,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
                 if ((unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W && c < p.Cin)
                     v = *reinterpret_cast<const f32x4*>(p.in + ((int64_t)iy * p.W + ix) * p.in_ld + c);
                 f16x4 hi, lo;
-                split4s(v, hi, lo);
+                otvm_split4(v, hi, lo);
                 *reinterpret_cast<f16x4*>(&Ph[pix * 8 + q * 4]) = hi;
                 *reinterpret_cast<f16x4*>(&Pl[pix * 8 + q * 4]) = lo;
             }

@@ -4,8 +4,8 @@
 // -ffp-contract=off so the elementwise arithmetic follows the reference's operation order exactly.
 #include "common.h"
 #include "head_math.h"
+#include "f16x3_ops.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {

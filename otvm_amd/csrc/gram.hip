@@ -22,12 +22,8 @@
 // pixels there (~1e-6 of unbiased noise per entry, far below the operands' own), and the per-workgroup partials -- one per
 // (block of the matrix, pixel chunk) -- are added in fp64 by gn_predict_kernel, which also contracts them with M_g.
 #include "common.h"
+#include "f16x3_ops.h"
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 

@@ -5,9 +5,8 @@
 //   apply : y = act((x - mean)*rstd*gamma + beta [+ residual]); per-channel scale/shift are built
 //           once per block in LDS from the fp64 sums.
 #include "common.h"
+#include "f16x3_ops.h"
 #include <stdlib.h>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 

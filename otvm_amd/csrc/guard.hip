@@ -8,8 +8,7 @@
 // frame number) at which an element failed |x| < limit in *flag (initialised to INT32_MAX by the caller); the host looks at
 // the flag whenever it synchronises anyway.
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "f16x3_ops.h"
 
 namespace {
 

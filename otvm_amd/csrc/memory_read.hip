@@ -18,9 +18,7 @@
 //             (128 AGPRs); A = P from LDS (b128, K-permuted), B = V straight from global/L2 (each
 //             element is used by exactly one wave, so staging it in LDS would buy nothing).
 #include "common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "f16x3_ops.h"
 
 namespace {
 

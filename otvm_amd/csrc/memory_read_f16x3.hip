@@ -17,12 +17,8 @@
 // boundaries) so that queries/64 x chunks fills the chip's 512 resident workgroups evenly: one workgroup per
 // (64 queries, slot) gave 640 workgroups at 1080p / T = 5, i.e. a second round at 25 % occupancy (2.16 -> 1.4 ms).
 #include "common.h"
+#include "f16x3_ops.h"
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -36,11 +32,6 @@ constexpr int LDPH = BKV + 8;     // halfs per P row (144 B)
 // denormal results -- a third of this kernel's VALU work.  e^(-inf) = 0 as before.
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 
-__device__ __forceinline__ void split1(float v, _Float16& hi, _Float16& lo) {
-    hi = (_Float16)v;
-    lo = (_Float16)(v - (float)hi);
-}
-
 // ---- bank packing: fp32 [hw,128] / [hw,512] -> fragment-major split fp16 -------------------------------
 __global__ __launch_bounds__(256) void bank_pack_keys_kernel(const float* __restrict__ k, int hw, _Float16* __restrict__ kf) {
     // one block per 32-row kv block: 8 d-blocks x 2 (hi/lo) x 64 lanes x 8 halfs
@@ -53,7 +44,7 @@ __global__ __launch_bounds__(256) void bank_pack_keys_kernel(const float* __rest
         for (int j = 0; j < 8; ++j) {
             const float v = row < hw ? k[(int64_t)row * DK + d0 + j] : 0.f;
             _Float16 h, lw;
-            split1(v, h, lw);
+            otvm_split1(v, h, lw);
             hi[j] = h; lo[j] = lw;
         }
         _Float16* base = kf + (((int64_t)kvb * 8 + db) * 2) * 512;
@@ -73,7 +64,7 @@ __global__ __launch_bounds__(256) void bank_pack_vals_kernel(const float* __rest
         for (int j = 0; j < 8; ++j) {
             const float x = (r0 + j) < hw ? v[(int64_t)(r0 + j) * DV + dv] : 0.f;
             _Float16 h, lw;
-            split1(x, h, lw);
+            otvm_split1(x, h, lw);
             hi[j] = h; lo[j] = lw;
         }
         _Float16* base = vf + (((int64_t)kvb * 16 + nb) * 2) * 512;
@@ -112,7 +103,7 @@ __global__ __launch_bounds__(256, 2) void memory_read_f16x3_kernel(const Mem3Arg
         if (q0 + r < hw) v = *reinterpret_cast<const f32x4*>(p.q + (int64_t)(q0 + r) * p.q_ld + c);
         f16x4 hi, lo;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { _Float16 h, lw; split1(v[j], h, lw); hi[j] = h; lo[j] = lw; }
+        for (int j = 0; j < 4; ++j) { _Float16 h, lw; otvm_split1(v[j], h, lw); hi[j] = h; lo[j] = lw; }
         *reinterpret_cast<f16x4*>(&Qh[r * LDQH + c]) = hi;
         *reinterpret_cast<f16x4*>(&Ql[r * LDQH + c]) = lo;
     }
@@ -211,7 +202,7 @@ __global__ __launch_bounds__(256, 2) void memory_read_f16x3_kernel(const Mem3Arg
                     const float e = fast_exp(v[4 * g + j] - m_new);
                     sum += e;
                     _Float16 h, lw;
-                    split1(e, h, lw);
+                    otvm_split1(e, h, lw);
                     hi[j] = h; lo[j] = lw;
                 }
                 const int kvl = sa * 32 + 8 * g + 4 * fh;

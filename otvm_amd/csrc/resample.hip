@@ -1,8 +1,7 @@
 // Pooling / resampling kernels on NHWC fp32 (HBM-bound, 16-byte accesses along channels).
 #include "common.h"
+#include "f16x3_ops.h"
 #include <stdlib.h>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 

@@ -562,3 +562,35 @@ def test_size_path_cases_reach_every_selected_path():
         # starts a slot instead of wrapping into it); every other case has chunks that wrap
         assert (lau[0]["crossing"] > 0) == ((hw, T) != (8160, 2)), (hw, T, lau)
     assert sum(len(mr_launches(T, hw)) > 1 for hw, T in MR_SHAPES) >= 2
+
+
+# ---- the implicit-GEMM tile table (csrc/conv_f16x3_kernel.h: IGEMM_TILES): what the library offers the plan-time tuner
+def test_conv_candidates_match_the_recorded_lists():
+    """otvm_conv2d_candidates (host code, nothing launched) returns, order included, the lists tests/golden/conv_candidates.json
+    recorded from the commit BEFORE the tile table was introduced (tests/golden/make_conv_candidates.py), for every layer shape
+    of the two r06 autotune profiles and every combination of w_wfrag / split-K workspace / precision / fused input norm; the
+    f16x3 lists once more from the probes build with both LDS-DMA forms offered (the compiled-in switches list 64 + t in place
+    of 32 + t).  The fixture must reach every tile in every form it has -- a form no list holds would pass unseen otherwise."""
+    import json
+    from otvm_amd import lib as L
+    from tests.golden import make_conv_candidates as mk
+    fx = json.load(open(mk.OUT))
+    assert fx["splitk_ws_bytes"] == mk.SPLITK_WS_BYTES
+    lib = L.load()
+    both = mk.record_both_forms(L.LIB_PATH)
+    seen = {1: set(), 2: set()}                                             # precision -> tile ids (form offset included)
+    for part, precs in (("cases", (1, 2)), ("cases_both_forms", (1,))):
+        assert [c["shape"] for c in fx[part]] == list(mk.shapes())          # every profile shape (and the extra ones), none dropped
+        for i, c in enumerate(fx[part]):
+            vs = [v for v in mk.variants(c["shape"]) if v[2] in precs]
+            assert sorted(c["lists"]) == sorted(mk.key(v) for v in vs), c["shape"]
+            for v in vs:
+                want = c["lists"][mk.key(v)]
+                got = mk.candidates(lib, mk.conv_params(c["shape"], *v)) if part == "cases" else both[i]["lists"][mk.key(v)]
+                assert got == want, (part, c["shape"], mk.key(v))
+                seen[v[2]] |= {code // 16 - 1 for code in want}
+    forms = [0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 11]                             # the tiles of the kernel template (13: forced only)
+    assert seen[1] >= set(range(12)) | {12, 14}, sorted(seen[1])            # staged 0-11 (9 = the one-wave tile), stem, patch
+    assert seen[1] >= {32 + t for t in forms} | {64 + t for t in forms}, sorted(seen[1])
+    assert seen[2] >= set(forms) | {32 + t for t in forms}, sorted(seen[2])
+    assert 13 not in seen[1] | seen[2] and not any(t >= 64 for t in seen[2])

@@ -25,9 +25,8 @@ def short(name):
     return re.sub(r"\(.*\)$", "", d)[:110]
 
 
-def main():
-    build = os.path.join(ROOT, "otvm_amd", "csrc", "build")
-    rows = []
+def code_objects(build):
+    """(object file, kernel metadata notes, disassembly) of the gfx950 code object of every object under ``build``."""
     with tempfile.TemporaryDirectory() as tmp:
         for o in sorted(f for f in os.listdir(build) if f.endswith(".o")):
             fat, co = os.path.join(tmp, "fat.bin"), os.path.join(tmp, "k.co")
@@ -39,22 +38,39 @@ def main():
                                    "--input=" + fat, "--output=" + co, "--unbundle"])
             notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True)
             dis = subprocess.check_output([os.path.join(LLVM, "llvm-objdump"), "-d", co], text=True)
-            scr = {}
-            cur = None
-            for line in dis.splitlines():
-                m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)
-                if m:
-                    cur = m.group(1)
-                elif cur and "scratch_" in line:
-                    scr[cur] = scr.get(cur, 0) + 1
-            for blk in notes.split("  - .agpr_count:")[1:]:
-                def f(key):
-                    m = re.search(r"\.%s:\s+(\S+)" % key, blk)
-                    return m.group(1) if m else "?"
-                name = f("name")
-                rows.append((o, name, int(f("vgpr_count")), int(blk.split()[0]), int(f("sgpr_count")), int(f("group_segment_fixed_size")),
-                             int(f("private_segment_fixed_size")), int(f("vgpr_spill_count")), scr.get(name, 0)))
             os.remove(fat)
+            yield o, notes, dis
+
+
+def functions(dis):
+    """{symbol: [disassembly lines]} of a llvm-objdump -d listing."""
+    out, cur = {}, None
+    for line in dis.splitlines():
+        m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)
+        if m:
+            cur = out.setdefault(m.group(1), [])
+        elif cur is not None and line.strip():
+            cur.append(line)
+    return out
+
+
+def resources(notes, dis):
+    """[(kernel, VGPR, AGPR, SGPR, static LDS B, scratch B, spilled VGPRs, scratch instructions)] of one code object."""
+    scr = {name: sum("scratch_" in line for line in body) for name, body in functions(dis).items()}
+    rows = []
+    for blk in notes.split("  - .agpr_count:")[1:]:
+        def f(key):
+            m = re.search(r"\.%s:\s+(\S+)" % key, blk)
+            return m.group(1) if m else "?"
+        name = f("name")
+        rows.append((name, int(f("vgpr_count")), int(blk.split()[0]), int(f("sgpr_count")), int(f("group_segment_fixed_size")),
+                     int(f("private_segment_fixed_size")), int(f("vgpr_spill_count")), scr.get(name, 0)))
+    return rows
+
+
+def main():
+    build = os.path.join(ROOT, "otvm_amd", "csrc", "build")
+    rows = [(o,) + r for o, notes, dis in code_objects(build) for r in resources(notes, dis)]
     print("# kernel resources of otvm_amd/libotvm_hip.so (gfx950), read from the built code objects by tools/isa_audit.py")
     print("# object | kernel | VGPR | AGPR | SGPR | static LDS B | scratch B | spilled VGPRs | scratch instructions")
     for r in rows:
