@@ -61,7 +61,10 @@ const char* otvm_last_error(void);
                                      predicted statistics); implicit-GEMM tiles 32 + t with LDS-DMA weight stages and 64 + t = the same on
                                      v_mfma_f32_16x16x32_f16 (tune codes; no new entry points);
                                  20: otvm_matting_grad_conn / _ws_bytes / _params (Grad and Conn matting metrics);
-                                 21: otvm_optflow_farneback / _ws_bytes / _params, otvm_matting_messddt (MESSDdt) */
+                                 21: otvm_optflow_farneback / _ws_bytes / _params, otvm_matting_messddt (MESSDdt);
+                                 (21, additive: the foreground outputs -- the entry points with _fgr in their names and the output
+                                  kernel of otvm_fgr_params are NEW symbols only; no existing struct, prototype or result changed, so a
+                                  caller built against the earlier 21 runs unchanged and the number stays) */
 int otvm_abi_version(void);
 
 /* ---------------------------------------------------------------- weights (load time) ----------
@@ -184,6 +187,11 @@ typedef struct otvm_head_params {
                                                        N = the 16 real output channels instead of a half-empty 32-wide tile   */
 } otvm_head_params;
 int otvm_conv2d_head(const otvm_conv_params* p, const otvm_head_params* h, void* stream);
+/* The same launch, keeping the head's foreground estimate as well: fgr = planar [3][P] fp32 over the padded frame, R, G, B --
+ * the clamped fused F of fba_fusion (FBA/models.py:281-284), the value the B update and the final alpha read; image b of a batch
+ * at fgr + b * fgr_bs.  A compile-time form of the same two kernels (16-wide / 32-wide, chosen as above): alpha, trimap, sm and
+ * the hidden state are bit-identical to the call without it; pixels outside the image are not written.                        */
+int otvm_conv2d_head_fgr(const otvm_conv_params* p, const otvm_head_params* h, float* fgr, int64_t fgr_bs, void* stream);
 int64_t otvm_head16_weight_bytes_f16x3(void);
 /* w_packed = otvm_pack_conv_weight's output of a 3x3 layer with I_pad == 32 and 16 filters, w_scale = its split scale */
 int otvm_pack_head16_weight_f16x3(const float* w_packed, int O, int K_pad, int I_pad, const float* w_scale, void* w16, void* stream);
@@ -433,11 +441,38 @@ int otvm_trimap_encode(const float* probs, int Hp, int Wp, const uint8_t* cls_ov
 int otvm_fba_head(const float* hid, int hid_ld, const float* w, const float* b, int n_out, const float* img,
                   int img_ld, int64_t P, float* alpha_out, int alpha_stride, float* tri_out, float* sm, int sm_ld,
                   void* stream);
+/* ... keeping the clamped fused F as well: fgr planar [3][P], R, G, B (see the _fgr form of the fused layer above)     */
+int otvm_fba_head_fgr(const float* hid, int hid_ld, const float* w, const float* b, int n_out, const float* img,
+                      int img_ld, int64_t P, float* alpha_out, int alpha_stride, float* tri_out, float* sm, int sm_ld,
+                      float* fgr, void* stream);
 
 /* crop the padding and produce the returned tensors (alpha/model.py:495-508, eval.py:209):
  * alpha [H,W] fp32, alpha_u8 [H,W] = trunc(alpha*255) (may be NULL), trimap [3,H,W] (may be NULL) */
 int otvm_crop_outputs(const float* alpha_p, const float* tri_p, int Hp, int Wp, int H, int W, int lh, int lw,
                       float* alpha, uint8_t* alpha_u8, float* tri, void* stream);
+
+/* Foreground outputs of one frame in one pass: reads the padded alpha plane and the three padded F planes once and writes
+ * whichever outputs are requested (NULL = not written).  All arithmetic is fp32, one IEEE operation per step (no contraction):
+ *   fgr      [3,H,W] fp32, R, G, B : F cropped, unchanged
+ *   rgba_u8  [H,W,4] : colour = q(F), A = q(alpha), q(v) = (uint8) min(max(trunc(v * 255.f), 0), 255) -- for alpha in [0,1] the
+ *                      byte otvm_crop_outputs writes as alpha_u8.  Straight (not premultiplied) alpha
+ *   comp_u8  [H,W,3] : bgf = (float)bg * (1.f / 255.f); c = (F * a) + (bgf * (1.f - a)); byte = q(c)
+ * A non-finite operand (F, alpha, or the composite c) gives byte 0 (converting NaN to an integer is undefined in C; here it is
+ * an explicit select).  bg_u8 = uint8 [H,W,3] of the frame's resolution, or NULL: the solid colour bg_color.  The three colour
+ * bytes of rgba_u8 / comp_u8, bg_u8 and bg_color are in B, G, R order (u8_rgb == 0, as decoded frames are) or R, G, B
+ * (u8_rgb != 0), as otvm_preprocess_params.u8_rgb has it.  No atomics: two calls give equal bits.                           */
+typedef struct otvm_fgr_params {
+    const float* alpha_p;         /* padded fused alpha [Hp*Wp] (needed for rgba_u8 / comp_u8)                    */
+    const float* fgr_p;           /* padded F planes [3][Hp*Wp], R, G, B                                          */
+    int Hp, Wp, H, W, lh, lw;     /* padded size, output size, top / left padding                                 */
+    float* fgr;
+    unsigned char* rgba_u8;
+    unsigned char* comp_u8;
+    const unsigned char* bg_u8;
+    unsigned char bg_color[3];
+    int u8_rgb;
+} otvm_fgr_params;
+int otvm_fgr_outputs(const otvm_fgr_params* p, void* stream);
 
 /* first-frame trimap from a GT alpha (alpha/model.py:342-362): unknown = dilate(0<a<1) with a
  * (2r+1)^2 max filter, fg = (a==1), bg = (a==0); out planar one-hot [3,H,W]; ws >= H*W bytes      */

@@ -5,6 +5,7 @@ Same constructor (``dilate_kernel, trimap, stage``), same 785-key ``state_dict``
 max_memory_num=2, large_input=False)`` returning the same 5-tuple.  All device work goes through
 ``libotvm_hip.so``; there is no PyTorch/CPU fallback -- on a CPU device ``forward`` raises.
 """
+import numpy as np
 import torch
 from torch import nn
 
@@ -31,6 +32,11 @@ class EvalModel(nn.Module):
         self._engine = None
         self._engine_key = None
         self.precision = None                     # None -> OTVM_PRECISION env or "f16x3"; "f32" = exact-fp32 MFMA
+        # extension (not part of the reference surface): keep the refinement head's foreground estimate F and publish, per
+        # frame, engine.last_fgr ([3,H,W] fp32 RGB), last_rgba_u8 ([H,W,4]) and, with set_background, last_comp_u8 ([H,W,3]).
+        # Read at a clip's first frame; forward's signature and 5-tuple do not change.
+        self.foreground = False
+        self._background = None
 
     # -- engine lifetime: rebuilt when the weights change or the module moves
     def _get_engine(self):
@@ -44,6 +50,30 @@ class EvalModel(nn.Module):
             self._engine = HipEngine(self.state_dict(), dev, precision=self.precision)
             self._engine_key = key
         return self._engine
+
+    def set_background(self, bg):
+        """What ``last_comp_u8`` is composited over (``foreground`` on): None = no composite; a TUPLE (c0, c1, c2) = a colour; a
+        uint8 [H,W,3] tensor / array = an image of the frames' resolution; a LIST = one of those per sequence of
+        ``forward_batch``.  Colours and images are in the frames' channel order (B, G, R unless the frames are RGB).  May
+        change between frames."""
+        self._background = [self._one_background(x) for x in bg] if isinstance(bg, list) else self._one_background(bg)
+
+    def _one_background(self, bg):
+        if bg is None:
+            return None
+        if isinstance(bg, tuple):
+            c = tuple(int(x) for x in bg)
+            if len(c) != 3 or not all(0 <= x <= 255 for x in c):
+                raise ValueError("otvm_amd: a background colour is three values in 0..255, got %r" % (bg,))
+            return c
+        t = bg if torch.is_tensor(bg) else torch.from_numpy(np.ascontiguousarray(bg))
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[-1] != 3:
+            raise ValueError("otvm_amd: a background image is uint8 [H,W,3], got %s %s" % (t.dtype, tuple(t.shape)))
+        return t.to(self.IMG_MEAN.device).contiguous()
+
+    def _push_options(self, eng):
+        eng.foreground = bool(self.foreground)
+        eng.background = self._background
 
     @property
     def memories(self):
@@ -61,6 +91,7 @@ class EvalModel(nn.Module):
             # alpha/model.py:395-396: unreachable from eval.py (EvalDataset is built with trimap=None, eval.py:133)
             raise NotImplementedError("per-frame `tri` input is not part of the reference eval path")
         eng = self._get_engine()
+        self._push_options(eng)
         out = eng.frame(a, fg, bg, tri_gt=tri_gt, first_frame=bool(first_frame), last_frame=bool(last_frame),
                         memorize=bool(memorize), max_memory_num=int(max_memory_num),
                         dilate_kernel=self.DILATION_KERNEL, frame_id=_frame_id, cls_override=_cls_override,
@@ -77,6 +108,7 @@ class EvalModel(nn.Module):
         over the B images, which fills the chip on the small maps a single sequence leaves mostly idle.  Returns a list of
         B 5-tuples; each equals what ``forward`` returns for that sequence run alone with the same kernel configurations."""
         eng = self._get_engine()
+        self._push_options(eng)
         out = eng.frame_batch(list(a), list(fg), list(bg), list(tri_gt), first_frame=bool(first_frame), last_frame=bool(last_frame),
                               memorize=bool(memorize), max_memory_num=int(max_memory_num), dilate_kernel=self.DILATION_KERNEL,
                               cls_override=_cls_override, frames_rgb=bool(_frames_rgb), inputs_ready=_inputs_ready)

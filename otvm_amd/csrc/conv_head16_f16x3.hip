@@ -25,7 +25,7 @@ struct Head16Args {
     unsigned in_bytes;                   // size of one image's input view (buffer-resource range)
     int tiles_x, tiles_y; OtvmTileWalk walk;
     int64_t in_bs, out_bs;
-    OtvmHeadArgs head; int64_t head_img_bs, head_alpha_bs, head_tri_bs, head_sm_bs;
+    OtvmHeadArgs head; int64_t head_img_bs, head_alpha_bs, head_tri_bs, head_sm_bs, head_fgr_bs;
 };
 
 constexpr int TH = 8, TW = 32, PH = TH + 2, PW = TW + 2, NPIX = PH * PW;
@@ -53,14 +53,16 @@ constexpr int EPL = 20;                  // floats per epilogue row: 16 channels
 #endif
 // N_OUT = 7 / 10: the head's width (its loops unrolled without run-time tests); FAST = the layer as the frame issues it --
 // LeakyReLU and a bias -- with the epilogue's constants (filter scales, bias) read as whole vectors; the generic form keeps the
-// run-time activation switch.
+// run-time activation switch.  FGR = the form that also keeps the head's foreground estimate (head.fgr, three fp32 planes: one lane
+// per pixel along the tile's 32-pixel rows, i.e. whole 128-byte segments per plane and row); the frame issues it only when the
+// engine's `foreground` option is on, the other instantiations do not read the field.
 // Round 5 (tools/head_bench.py, profiles/r05_head16_ablation.txt): the per-pixel head cost 67 of the launch's 174 us, and not for
 // its arithmetic -- its 170 weights were fetched by (wave-uniform) GLOBAL loads inside the epilogue, each batch waited for with
 // vmcnt(0) right where it was issued, the pixel's RGB likewise, and the sixteen filter scales / biases one s_load + wait + branch
 // each (the run-time `act` switch and `if (bias)` per element kept the compiler from batching them).  Now: every thread fetches
 // ONE of the head's weights and its pixel's RGB at the top of the kernel (the latency passes under the patch load and the tap
 // loop), the weights go through 680 bytes of LDS behind the epilogue rows and are read as broadcast ds_read_b128.
-template <int N_OUT, bool FAST>
+template <int N_OUT, bool FAST, bool FGR>
 __global__ __launch_bounds__(256, OTVM_HEAD16_WGS) void conv_head16_f16x3_kernel(const Head16Args pa) {
     Head16Args p = pa;
     {
@@ -71,6 +73,7 @@ __global__ __launch_bounds__(256, OTVM_HEAD16_WGS) void conv_head16_f16x3_kernel
         if (p.head.alpha_out) p.head.alpha_out += zb * p.head_alpha_bs;
         if (p.head.tri_out) p.head.tri_out += zb * p.head_tri_bs;
         if (p.head.sm) p.head.sm += zb * p.head_sm_bs;
+        if constexpr (FGR) { if (p.head.fgr) p.head.fgr += zb * p.head_fgr_bs; }
     }
     constexpr int PATCH_HALFS = 2 * NPIX * LDP;                  // hi + lo
     constexpr int EPI_HALFS = 4 * 2 * 32 * EPL * 2;              // four waves x two rows x 32 pixels (fp32, in halfs)
@@ -229,7 +232,7 @@ __global__ __launch_bounds__(256, OTVM_HEAD16_WGS) void conv_head16_f16x3_kernel
 #elif OTVM_H16_NOSTORE
         { OtvmHeadArgs q = p.head; q.tri_out = nullptr; q.sm = nullptr; otvm_head_pixel_w<N_OUT, const lds_float*>(h, q, em, hw, hw + N_OUT * 16, eim); }
 #else
-        otvm_head_pixel_w<N_OUT, const lds_float*>(h, p.head, em, hw, hw + N_OUT * 16, eim);
+        otvm_head_pixel_w<N_OUT, const lds_float*, FGR>(h, p.head, em, hw, hw + N_OUT * 16, eim);
 #endif
     }
 }
@@ -261,8 +264,20 @@ extern "C" int otvm_pack_head16_weight_f16x3(const float* w_packed, int O, int K
     return 0;
 }
 
-// called by otvm_conv2d_head (conv_patch_f16x3.hip) when the head's 16-wide weights are given; p validated there
-int otvm_conv2d_head16_impl(const otvm_conv_params* p, const otvm_head_params* hd, void* stream) {
+template <bool FGR>
+static void launch_head16(const Head16Args& a, int n_out, bool fast, dim3 grid, hipStream_t s) {
+    if (n_out == 7) {
+        if (fast) hipLaunchKernelGGL((conv_head16_f16x3_kernel<7, true, FGR>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((conv_head16_f16x3_kernel<7, false, FGR>), grid, dim3(256), 0, s, a);
+    } else {
+        if (fast) hipLaunchKernelGGL((conv_head16_f16x3_kernel<10, true, FGR>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((conv_head16_f16x3_kernel<10, false, FGR>), grid, dim3(256), 0, s, a);
+    }
+}
+
+// called by otvm_conv2d_head / otvm_conv2d_head_fgr (conv_patch_f16x3.hip) when the head's 16-wide weights are given; p validated
+// there.  fgr: nullptr = the kernels of otvm_conv2d_head, unchanged
+int otvm_conv2d_head16_impl(const otvm_conv_params* p, const otvm_head_params* hd, float* fgr, int64_t fgr_bs, void* stream) {
     OTVM_REQUIRE(p->Cin == 32 && p->Cout == 16 && (p->in_ld & 3) == 0 && ((uintptr_t)p->in & 15) == 0 && !p->in_scale && !p->in_relu,
                  "otvm_conv2d_head (16-wide tile): 32 input channels, plain input");
     Head16Args a;
@@ -277,19 +292,15 @@ int otvm_conv2d_head16_impl(const otvm_conv_params* p, const otvm_head_params* h
     a.head.w = hd->w; a.head.b = hd->b; a.head.n_out = hd->n_out; a.head.img = hd->img; a.head.img_ld = hd->img_ld;
     a.head.P = hd->P; a.head.alpha_out = hd->alpha_out; a.head.alpha_stride = hd->alpha_stride; a.head.tri_out = hd->tri_out;
     a.head.sm = hd->sm; a.head.sm_ld = hd->sm_ld; a.head.out7 = nullptr; a.head.logits_out = nullptr;
+    a.head.fgr = fgr; a.head_fgr_bs = batch > 1 ? fgr_bs : 0;
     a.head_img_bs = batch > 1 ? hd->img_bs : 0; a.head_alpha_bs = batch > 1 ? hd->alpha_bs : 0;
     a.head_tri_bs = batch > 1 ? hd->tri_bs : 0; a.head_sm_bs = batch > 1 ? hd->sm_bs : 0;
     OTVM_REQUIRE(hd->n_out == 7 || hd->n_out == 10, "otvm_conv2d_head (16-wide tile): a head of 7 or 10 outputs (got %d)", hd->n_out);
     const dim3 grid(a.tiles_x * a.tiles_y, batch);
     hipStream_t s = (hipStream_t)stream;
     const bool fast = p->act == OTVM_ACT_LEAKY && p->bias && ((uintptr_t)p->bias & 15) == 0 && ((uintptr_t)p->w_scale & 15) == 0;
-    if (hd->n_out == 7) {
-        if (fast) hipLaunchKernelGGL((conv_head16_f16x3_kernel<7, true>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((conv_head16_f16x3_kernel<7, false>), grid, dim3(256), 0, s, a);
-    } else {
-        if (fast) hipLaunchKernelGGL((conv_head16_f16x3_kernel<10, true>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((conv_head16_f16x3_kernel<10, false>), grid, dim3(256), 0, s, a);
-    }
+    if (fgr) launch_head16<true>(a, hd->n_out, fast, grid, s);
+    else launch_head16<false>(a, hd->n_out, fast, grid, s);
     OTVM_CHECK_LAUNCH("otvm_conv2d_head (16-wide tile)");
     return 0;
 }

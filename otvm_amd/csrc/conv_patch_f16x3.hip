@@ -70,7 +70,7 @@ struct PatchArgs {
     unsigned in_bytes, in_res_bytes;     // round 5: sizes of one image's input / identity views (buffer-resource ranges)
     // ABI 17 (HEAD kernels, 16 output channels): the 1x1 head + fba_fusion of the FBA decoder / refinement run in the epilogue
     // on the pixel's 16 hidden values (head_math.h); out (the hidden state) is optional then
-    OtvmHeadArgs head; int64_t head_img_bs, head_alpha_bs, head_tri_bs, head_sm_bs;
+    OtvmHeadArgs head; int64_t head_img_bs, head_alpha_bs, head_tri_bs, head_sm_bs, head_fgr_bs;
 };
 
 constexpr int CB = 16;           // channels per stage = one MFMA k-step
@@ -114,7 +114,7 @@ __device__ __forceinline__ int pi16(int r) {
 // bank slots for ANY tap offset, and the staging ds_write_b64 (four pixels x four quads per 16 lanes) is conflict-free too.
 // B fragments come from the unchanged 1-KiB blocks: slot (lane & 15) + 16 sj + 32 (octet & 1) of tap t or t + 1.
 template <int TH, int BN, int NW, int DIL, int TAPG, bool INRES = false, bool HEAD = false, int NWN = 1, bool GLDS = false, int NPASS = 3,
-          bool M16 = false>
+          bool M16 = false, bool FGR = false>
 __global__ __launch_bounds__(NW * 64)
 __attribute__((amdgpu_waves_per_eu((TAPG == 3 && BN <= 32 && !INRES) ? 3 : (M16 ? 2 : 1), (TAPG == 3 && BN <= 32 && !INRES) ? 3 : 10)))
 void conv_patch_f16x3_kernel(const PatchArgs pa) {
@@ -128,6 +128,7 @@ void conv_patch_f16x3_kernel(const PatchArgs pa) {
             if (p.head.alpha_out) p.head.alpha_out += zb * p.head_alpha_bs;
             if (p.head.tri_out) p.head.tri_out += zb * p.head_tri_bs;
             if (p.head.sm) p.head.sm += zb * p.head_sm_bs;
+            if constexpr (FGR) { if (p.head.fgr) p.head.fgr += zb * p.head_fgr_bs; }
         }
         p.out += zb * p.out_bs;
         if (p.residual) p.residual += zb * p.res_bs;
@@ -145,6 +146,7 @@ void conv_patch_f16x3_kernel(const PatchArgs pa) {
     constexpr int PW = 32 + 2 * DIL, PH = TH + 2 * DIL, NPIX = PH * PW;
     constexpr int NG = 9 / TAPG;
     static_assert(BN % 32 == 0 && 9 % TAPG == 0, "bad tile");
+    static_assert(!FGR || HEAD, "FGR: the HEAD variant that also keeps the head's foreground estimate (head.fgr)");
     static_assert(!M16 || (TAPG == 9 && NPASS == 3 && !HEAD && NWN == 1 && !GLDS), "the 16x16x32 form: nine-tap f16x3 tiles");
     constexpr int PLANE = ((NPIX + 11) / 16) * 16 + 4;                 // M16: pixels per octet plane, = 4 mod 16 (>= NPIX)
     constexpr int PATCH_HALFS = M16 ? 2 * 2 * PLANE * 8 : 2 * NPIX * LDP;   // hi + lo
@@ -583,7 +585,7 @@ void conv_patch_f16x3_kernel(const PatchArgs pa) {
                 for (int k = 0; k < 4; ++k)
                     *reinterpret_cast<f32x4*>(p.out + m * p.out_ld + 4 * k) = f32x4{h[4 * k], h[4 * k + 1], h[4 * k + 2], h[4 * k + 3]};
             }
-            otvm_head_pixel(h, p.head, m);
+            otvm_head_pixel<FGR>(h, p.head, m);
         }
         return;
     }
@@ -856,13 +858,13 @@ __global__ __launch_bounds__(256) void pack_patch_weight_kernel(const float* __r
 }
 
 template <int NPASS, int TH, int BN, int NW, int DIL, int TAPG = 9, bool INRES = false, bool HEAD = false, int NWN = 1, bool GLDS = false,
-          bool M16 = false>
+          bool M16 = false, bool FGR = false>
 int launch_patch(PatchArgs& a, hipStream_t s) {
     a.tiles_x = otvm_ceil_div(a.W, 32);
     a.tiles_y = otvm_ceil_div(a.H, TH);
     a.tiles_n = otvm_ceil_div(a.Cout, BN);
     a.walk = otvm_tile_walk_of(1);
-    hipLaunchKernelGGL((conv_patch_f16x3_kernel<TH, BN, NW, DIL, TAPG, INRES, HEAD, NWN, GLDS, NPASS, M16>), dim3(a.tiles_x * a.tiles_y * a.tiles_n, a.batch), dim3(NW * 64), 0, s, a);
+    hipLaunchKernelGGL((conv_patch_f16x3_kernel<TH, BN, NW, DIL, TAPG, INRES, HEAD, NWN, GLDS, NPASS, M16, FGR>), dim3(a.tiles_x * a.tiles_y * a.tiles_n, a.batch), dim3(NW * 64), 0, s, a);
     OTVM_CHECK_LAUNCH("otvm_conv2d(patch f16x3)");
     return 0;
 }
@@ -925,19 +927,31 @@ int otvm_conv2d_patch_eligible(const otvm_conv_params* p) {
     return patch_choice(p, true) != 0 ? 1 : 0;
 }
 
-static int patch_run(const otvm_conv_params* p, void* stream, int choice, const otvm_head_params* hd = nullptr);
-int otvm_conv2d_head16_impl(const otvm_conv_params* p, const otvm_head_params* hd, void* stream);   // conv_head16_f16x3.hip
+static int patch_run(const otvm_conv_params* p, void* stream, int choice, const otvm_head_params* hd = nullptr, float* fgr = nullptr,
+                     int64_t fgr_bs = 0);
+int otvm_conv2d_head16_impl(const otvm_conv_params* p, const otvm_head_params* hd, float* fgr, int64_t fgr_bs, void* stream);   // conv_head16_f16x3.hip
 
-// ABI 17: 3x3 conv to 16 channels with the FBA head in its epilogue (include/otvm_hip.h)
-extern "C" int otvm_conv2d_head(const otvm_conv_params* p, const otvm_head_params* hd, void* stream) {
+// ABI 17: 3x3 conv to 16 channels with the FBA head in its epilogue (include/otvm_hip.h); fgr != nullptr: otvm_conv2d_head_fgr
+static int conv2d_head_any(const otvm_conv_params* p, const otvm_head_params* hd, float* fgr, int64_t fgr_bs, void* stream) {
     OTVM_REQUIRE(p && hd && p->in && hd->w && hd->b && hd->img, "otvm_conv2d_head: null pointer");
     OTVM_REQUIRE(otvm_prec_is_split(p->precision) && p->Cout == 16 && patch_choice(p) == 1 && p->dil == 1 && !p->residual &&
                      !p->gn_stats && !p->in_res && p->w_scale,
                  "otvm_conv2d_head: a 3x3 stride-1 f16x3 layer with 16 output channels, no residual / statistics");
     OTVM_REQUIRE(hd->n_out == 7 || (hd->n_out == 10 && hd->tri_out), "otvm_conv2d_head: n_out must be 7, or 10 with tri_out");
     OTVM_REQUIRE(!p->out || ((p->out_ld & 3) == 0 && ((uintptr_t)p->out & 15) == 0), "otvm_conv2d_head: out must be 16-byte aligned");
-    if (hd->w16) return otvm_conv2d_head16_impl(p, hd, stream);    // 32 -> 16 on the 16-wide matrix-core tile
-    return patch_run(p, stream, 1, hd);
+    if (hd->w16) return otvm_conv2d_head16_impl(p, hd, fgr, fgr_bs, stream);    // 32 -> 16 on the 16-wide matrix-core tile
+    return patch_run(p, stream, 1, hd, fgr, fgr_bs);
+}
+
+extern "C" int otvm_conv2d_head(const otvm_conv_params* p, const otvm_head_params* hd, void* stream) {
+    return conv2d_head_any(p, hd, nullptr, 0, stream);
+}
+
+// The same layer, keeping the head's foreground estimate as well (the FGR forms of the two kernels); route chosen as above
+extern "C" int otvm_conv2d_head_fgr(const otvm_conv_params* p, const otvm_head_params* hd, float* fgr, int64_t fgr_bs, void* stream) {
+    OTVM_REQUIRE(fgr && hd && hd->P > 0 && ((p && p->batch > 1) ? fgr_bs >= 3 * hd->P : true),
+                 "otvm_conv2d_head_fgr: fgr must be given, [3][P] per image (fgr_bs >= 3 P for a batch)");
+    return conv2d_head_any(p, hd, fgr, fgr_bs, stream);
 }
 
 int otvm_conv2d_patch_f16x3_forced(const otvm_conv_params* p, void* stream) { return patch_run(p, stream, patch_choice(p, true)); }
@@ -953,7 +967,7 @@ static int patch_m16() {
 }
 
 template <int NPASS>
-static int patch_run_t(const otvm_conv_params* p, void* stream, int choice, const otvm_head_params* hd) {
+static int patch_run_t(const otvm_conv_params* p, void* stream, int choice, const otvm_head_params* hd, float* fgr, int64_t fgr_bs) {
     if (choice == 0) return -1;
     const bool is_wide = choice == 2;
     PatchArgs a;
@@ -979,6 +993,8 @@ static int patch_run_t(const otvm_conv_params* p, void* stream, int choice, cons
         a.head.sm = hd->sm; a.head.sm_ld = hd->sm_ld; a.head.out7 = nullptr; a.head.logits_out = nullptr;
         a.head_img_bs = a.batch > 1 ? hd->img_bs : 0; a.head_alpha_bs = a.batch > 1 ? hd->alpha_bs : 0;
         a.head_tri_bs = a.batch > 1 ? hd->tri_bs : 0; a.head_sm_bs = a.batch > 1 ? hd->sm_bs : 0;
+        a.head.fgr = fgr; a.head_fgr_bs = a.batch > 1 ? fgr_bs : 0;
+        if (fgr) return launch_patch<3, 8, 32, 4, 1, 3, false, true, 1, false, false, true>(a, s);
         return launch_patch<3, 8, 32, 4, 1, 3, false, true>(a, s);      // (the head epilogue: f16x3 in either mode)
     }
     if (p->in_res) {
@@ -1039,6 +1055,6 @@ static int patch_run_t(const otvm_conv_params* p, void* stream, int choice, cons
     return launch_patch<NPASS, 8, 64, 4, 4>(a, s);
 }
 
-static int patch_run(const otvm_conv_params* p, void* stream, int choice, const otvm_head_params* hd) {
-    return p->precision == OTVM_PREC_F16 ? patch_run_t<1>(p, stream, choice, hd) : patch_run_t<3>(p, stream, choice, hd);
+static int patch_run(const otvm_conv_params* p, void* stream, int choice, const otvm_head_params* hd, float* fgr, int64_t fgr_bs) {
+    return p->precision == OTVM_PREC_F16 ? patch_run_t<1>(p, stream, choice, hd, fgr, fgr_bs) : patch_run_t<3>(p, stream, choice, hd, fgr, fgr_bs);
 }

@@ -119,7 +119,10 @@ __global__ __launch_bounds__(256) void fba_head_kernel(const float* __restrict__
             const f32x4 v = *reinterpret_cast<const f32x4*>(hid + i * hid_ld + 4 * k);
             h[4 * k] = v.x; h[4 * k + 1] = v.y; h[4 * k + 2] = v.z; h[4 * k + 3] = v.w;
         }
-        otvm_head_pixel(h, q, i);
+        // one instantiation serves otvm_fba_head, otvm_fba_head_fgr and otvm_fba_head_train: whether F is kept is the run-time
+        // test of q.fgr inside (a wave-uniform branch, as out7's is) -- the existing two entry points gain that branch.  The
+        // fused kernels choose the FGR form at compile time and only with a pointer, so the same test is dead code there.
+        otvm_head_pixel<true>(h, q, i);
     }
 }
 
@@ -239,18 +242,33 @@ extern "C" int otvm_trimap_to_sm(const float* tri, int64_t P, float* sm, int sm_
     return 0;
 }
 
-extern "C" int otvm_fba_head(const float* hid, int hid_ld, const float* w, const float* b, int n_out, const float* img,
-                             int img_ld, int64_t P, float* alpha_out, int alpha_stride, float* tri_out, float* sm,
-                             int sm_ld, void* stream) {
+static int fba_head_any(const float* hid, int hid_ld, const float* w, const float* b, int n_out, const float* img,
+                        int img_ld, int64_t P, float* alpha_out, int alpha_stride, float* tri_out, float* sm,
+                        int sm_ld, float* fgr, void* stream) {
     OTVM_REQUIRE(n_out == 7 || n_out == 10, "otvm_fba_head: n_out must be 7 or 10 (got %d)", n_out);
     OTVM_REQUIRE(n_out == 7 || tri_out, "otvm_fba_head: tri_out required when n_out == 10");
     OTVM_REQUIRE(hid_ld % 4 == 0 && ((uintptr_t)hid & 15) == 0, "otvm_fba_head: hid view must be 16-byte aligned");
     OtvmHeadArgs q;
     q.w = w; q.b = b; q.n_out = n_out; q.img = img; q.img_ld = img_ld; q.P = P; q.alpha_out = alpha_out; q.alpha_stride = alpha_stride;
     q.tri_out = tri_out; q.sm = sm; q.sm_ld = sm_ld; q.out7 = nullptr; q.logits_out = nullptr;
+    q.fgr = fgr;
     hipLaunchKernelGGL(fba_head_kernel, dim3(grid_for(P)), dim3(256), 0, (hipStream_t)stream, hid, hid_ld, q);
     OTVM_CHECK_LAUNCH("otvm_fba_head");
     return 0;
+}
+
+extern "C" int otvm_fba_head(const float* hid, int hid_ld, const float* w, const float* b, int n_out, const float* img,
+                             int img_ld, int64_t P, float* alpha_out, int alpha_stride, float* tri_out, float* sm,
+                             int sm_ld, void* stream) {
+    return fba_head_any(hid, hid_ld, w, b, n_out, img, img_ld, P, alpha_out, alpha_stride, tri_out, sm, sm_ld, nullptr, stream);
+}
+
+// otvm_fba_head that also keeps the clamped fused F, planar [3][P] RGB (the unfused route and the f32 precision)
+extern "C" int otvm_fba_head_fgr(const float* hid, int hid_ld, const float* w, const float* b, int n_out, const float* img,
+                                 int img_ld, int64_t P, float* alpha_out, int alpha_stride, float* tri_out, float* sm,
+                                 int sm_ld, float* fgr, void* stream) {
+    OTVM_REQUIRE(fgr, "otvm_fba_head_fgr: fgr required");
+    return fba_head_any(hid, hid_ld, w, b, n_out, img, img_ld, P, alpha_out, alpha_stride, tri_out, sm, sm_ld, fgr, stream);
 }
 
 extern "C" int otvm_fba_head_train(const float* hid, int hid_ld, const float* w, const float* b, int n_out, const float* img,
@@ -260,7 +278,7 @@ extern "C" int otvm_fba_head_train(const float* hid, int hid_ld, const float* w,
     OTVM_REQUIRE(hid_ld % 4 == 0 && ((uintptr_t)hid & 15) == 0, "otvm_fba_head_train: hid view must be 16-byte aligned");
     OtvmHeadArgs q;
     q.w = w; q.b = b; q.n_out = n_out; q.img = img; q.img_ld = img_ld; q.P = P; q.alpha_out = nullptr; q.alpha_stride = 0;
-    q.tri_out = nullptr; q.sm = nullptr; q.sm_ld = 0; q.out7 = out7; q.logits_out = logits_out;
+    q.tri_out = nullptr; q.sm = nullptr; q.sm_ld = 0; q.out7 = out7; q.logits_out = logits_out; q.fgr = nullptr;
     hipLaunchKernelGGL(fba_head_kernel, dim3(grid_for(P)), dim3(256), 0, (hipStream_t)stream, hid, hid_ld, q);
     OTVM_CHECK_LAUNCH("otvm_fba_head_train");
     return 0;

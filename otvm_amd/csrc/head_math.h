@@ -12,6 +12,7 @@ struct OtvmHeadArgs {
     float* tri_out;                                      // [3][P] softmax of logits 7..9 (n_out == 10)
     float* sm; int sm_ld;                                // optional: (p_unknown, p_fg, alpha) -> sm[i * sm_ld + 3 .. 5]
     float* out7; float* logits_out;                      // training forward: fused (alpha, F, B) planar [7][P]; raw logits [3][P]
+    float* fgr;                                          // optional: the clamped fused F, planar [3][P] RGB (read by the FGR forms only)
 };
 
 __device__ __forceinline__ float otvm_sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
@@ -19,8 +20,9 @@ __device__ __forceinline__ float otvm_clamp01(float x) { return fminf(fmaxf(x, 0
 
 // N_OUT_T = 7 / 10: the head's width known at compile time (0: q.n_out at run time); WP = where the head's weights / bias are read
 // from -- `const float*` (global memory, wave-uniform addresses) or an LDS pointer (the 16-wide conv stages them once per
-// workgroup, round 5); im = the pixel's composited RGB, loaded by the caller (early, so that its latency is not exposed here)
-template <int N_OUT_T, typename WP>
+// workgroup, round 5); im = the pixel's composited RGB, loaded by the caller (early, so that its latency is not exposed here);
+// FGR = the form that keeps the foreground estimate: q.fgr (when set) receives the F the B update and the final alpha read
+template <int N_OUT_T, typename WP, bool FGR = false>
 __device__ __forceinline__ void otvm_head_pixel_w(const float (&h)[16], const OtvmHeadArgs& q, int64_t i, WP w, WP b, const float (&im)[3]) {
 #pragma clang fp contract(off)
     const int n_out = N_OUT_T ? N_OUT_T : q.n_out;
@@ -55,6 +57,12 @@ __device__ __forceinline__ void otvm_head_pixel_w(const float (&h)[16], const Ot
     }
     al = otvm_clamp01((al * 0.1f + num) / (den + 0.1f));
     if (q.alpha_out) q.alpha_out[i * q.alpha_stride] = al;
+    if constexpr (FGR) {
+        if (q.fgr) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) q.fgr[c * P + i] = F[c];
+        }
+    }
     if (q.out7) {                                           // training forward: the fused (alpha, F, B) of FBA/models.py:388
         q.out7[i] = al;
 #pragma unroll
@@ -83,7 +91,8 @@ __device__ __forceinline__ void otvm_head_pixel_w(const float (&h)[16], const Ot
     }
 }
 
+template <bool FGR = false>
 __device__ __forceinline__ void otvm_head_pixel(const float (&h)[16], const OtvmHeadArgs& q, int64_t i) {
     const float im[3] = {q.img[i * q.img_ld], q.img[i * q.img_ld + 1], q.img[i * q.img_ld + 2]};
-    otvm_head_pixel_w<0, const float*>(h, q, i, q.w, q.b, im);
+    otvm_head_pixel_w<0, const float*, FGR>(h, q, i, q.w, q.b, im);
 }

@@ -433,6 +433,17 @@ class HipEngine:
         self._diag_host = None
         self._diag_ev = None
         self.keep_hid_d = False      # training forward (otvm_amd/train.py): the decoder's hidden state must exist in memory
+        # Foreground outputs (opt-in): the refinement head keeps its fused F (otvm_conv2d_head_fgr / otvm_fba_head_fgr) and every
+        # frame ends with otvm_fgr_outputs behind otvm_crop_outputs.  `foreground` is read at a clip's first frame only (the
+        # plans of the two forms are distinct: different launch lists, different captured graphs); `background` = what comp_u8
+        # is composited over: None (no composite), a uint8 [H,W,3] device tensor, a colour triple, or a list of B of those
+        # for frame_batch -- in the channel order of the frames (B, G, R unless frames_rgb).  Results: last_fgr [3,H,W] fp32
+        # R, G, B; last_rgba_u8 [H,W,4]; last_comp_u8 [H,W,3] (or None); *_b = per image of a batch.  Fresh tensors per frame.
+        self.foreground = False
+        self.background = None
+        self._fgr_on = False
+        self.last_fgr = self.last_rgba_u8 = self.last_comp_u8 = None
+        self.last_fgr_b = self.last_rgba_u8_b = self.last_comp_u8_b = None
         global _TUNE_FILE_LOADED
         if not _TUNE_FILE_LOADED:
             _TUNE_FILE_LOADED = True
@@ -660,6 +671,8 @@ class HipEngine:
         key = (H, W) if B == 1 else (H, W, B)
         if self.keep_hid_d:
             key = key + ("hid_d",)
+        if self._fgr_on:
+            key = key + ("fgr",)
         if key not in self.plans:
             self.plans[key] = FramePlan(self, H, W, B)
         return self.plans[key]
@@ -746,6 +759,13 @@ class HipEngine:
             # caller's promise covers the tensor it passed, not this copy -- the side streams must order themselves behind
             # the launch stream (the conservative path), or the query encoder would read the copy before it is written
             inputs_ready = None
+        if first_frame:
+            # the two forms are two plans (own buffers, launch lists and captured graphs; a switch re-keys, nothing is patched in
+            # place); tuned convolutions are shared through their layer signatures -- the refinement's last conv is tuned on the
+            # unfused route only, where it is the same launch in both forms
+            self._fgr_on = bool(self.foreground) and train is None
+        elif bool(self.foreground) != self._fgr_on and train is None:
+            raise RuntimeError("otvm_amd: `foreground` may only change at a clip's first frame")
         pl = self.plan(H, W, B)
         stream = self._stream()
         outs = [dict(scaled_imgs=torch.empty((1, 1, 3, H, W), dtype=f32, device=dev),
@@ -966,6 +986,9 @@ class HipEngine:
                                           o["alpha"].data_ptr(), o["alpha_u8"].data_ptr(), o["tri_out"].data_ptr(), stream), "crop")
         self.last_alpha_u8 = outs[0]["alpha_u8"]
         self.last_alpha_u8_b = [o["alpha_u8"] for o in outs]
+        # (a first frame computed twice -- the conditioning guard below -- comes through here twice: what is published belongs
+        # to the frame that is returned)
+        self._fgr_outputs(pl, outs, H, W, u8 and frames_rgb, stream)
         self.last_plan = pl
         if pl._predicted and not self.gn_predict_off:
             # conditioning guard of the predicted GroupNorm statistics (see GN_PREDICT_KAPPA_*): a clip's first frame is checked
@@ -995,11 +1018,49 @@ class HipEngine:
         if self.check_finite and not all(bool(torch.isfinite(o["alpha"]).all()) for o in outs):
             raise FloatingPointError("otvm_amd: non-finite alpha at frame %d -- an activation probably left fp16's range on the "
                                      "f16x3 path; rerun with model.precision = 'f32' (exact-fp32 MFMA)" % frame_id)
+        if self.check_finite and pl.fgr and not all(bool(torch.isfinite(f).all()) for f in self.last_fgr_b):
+            raise FloatingPointError("otvm_amd: non-finite foreground at frame %d -- an activation probably left fp16's range on "
+                                     "the f16x3 path; rerun with model.precision = 'f32' (exact-fp32 MFMA)" % frame_id)
         if last_frame or self.check_finite:
             # end of the clip: the caller synchronises to collect its results -- the guard's verdict for the whole clip is
             # read here (the reference's loop synchronises after every frame, eval.py:195-197)
             self.guard_check(sync=True)
         return [(o["scaled_imgs"], o["tri_out"], o["tri_gt_out"], o["alpha"], ins[b][0]) for b, o in enumerate(outs)]
+
+    def _fgr_outputs(self, pl, outs, H, W, rgb, stream):
+        """otvm_fgr_outputs per image behind otvm_crop_outputs (same stream): F cropped, RGBA bytes, the composite."""
+        if not pl.fgr:
+            self.last_fgr = self.last_rgba_u8 = self.last_comp_u8 = None
+            self.last_fgr_b = self.last_rgba_u8_b = self.last_comp_u8_b = None
+            return
+        dev, B = self.dev, len(outs)
+        bgs = self.background if isinstance(self.background, list) else [self.background] * B
+        if len(bgs) != B:
+            raise ValueError("otvm_amd: %d backgrounds for a batch of %d sequences" % (len(bgs), B))
+        fl, rl, cl = [], [], []
+        for b in range(B):
+            q = L.FgrParams()
+            q.alpha_p, q.fgr_p = pl.ALPHA_P_B[b].data_ptr(), pl.FGR_P_B[b].data_ptr()
+            q.Hp, q.Wp, q.H, q.W, q.lh, q.lw = pl.Hp, pl.Wp, H, W, pl.lh, pl.lw
+            q.u8_rgb = int(bool(rgb))
+            fgr = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+            rgba = torch.empty((H, W, 4), dtype=torch.uint8, device=dev)
+            comp, bg = None, bgs[b]
+            q.fgr, q.rgba_u8 = fgr.data_ptr(), rgba.data_ptr()
+            if bg is not None:
+                comp = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+                q.comp_u8 = comp.data_ptr()
+                if torch.is_tensor(bg):
+                    if bg.dtype != torch.uint8 or tuple(bg.shape) != (H, W, 3) or bg.device != dev or not bg.is_contiguous():
+                        raise ValueError("otvm_amd: the background must be a contiguous uint8 [%d,%d,3] tensor on %s (got %s %s)"
+                                         % (H, W, dev, bg.dtype, tuple(bg.shape)))
+                    q.bg_u8 = bg.data_ptr()
+                else:
+                    q.bg_color[:] = [int(c) for c in bg]
+            L.check(self.lib.otvm_fgr_outputs(C.byref(q), stream), "fgr_outputs")
+            fl.append(fgr), rl.append(rgba), cl.append(comp)
+        self.last_fgr, self.last_rgba_u8, self.last_comp_u8 = fl[0], rl[0], cl[0]
+        self.last_fgr_b, self.last_rgba_u8_b, self.last_comp_u8_b = fl, rl, cl
 
     def _preprocess_rest(self, pl, pp, par, scaled_imgs, with_sq, stream, b=0):
         """otvm_preprocess of image ``b`` for everything but (with_sq False) the query encoder's input: the composite returned
@@ -1059,6 +1120,7 @@ class FramePlan:
         self.lib = eng.lib
         self.dev = eng.dev
         self.H, self.W, self.B = H, W, B
+        self.fgr = bool(eng._fgr_on)                          # the form that keeps the refinement head's foreground estimate
         if B > 1 and eng.precision != L.PREC_F16X3:
             raise NotImplementedError("otvm_amd: batched sequences (B > 1) run on the f16x3 path only")
         self.lw, self.uw, self.lh, self.uh = pad_amounts(H, W, 32)
@@ -1275,10 +1337,12 @@ class FramePlan:
         S.append((self.lib.otvm_conv2d, (C.byref(p),), "conv " + wname, flops, abytes, (x, out.ch(0, _rup(w.O, 4)) if out.C >= _rup(w.O, 4) else out)))
         return p
 
-    def conv_head(self, S, x, wname, hid_out, head_w, head_b, n_out, img, alpha, alpha_stride, alpha_bs, tri=None, sm=None):
+    def conv_head(self, S, x, wname, hid_out, head_w, head_b, n_out, img, alpha, alpha_stride, alpha_bs, tri=None, sm=None,
+                  fgr=None):
         """3x3 conv 32 -> 16 + LeakyReLU with the FBA head in its epilogue (otvm_conv2d_head).  hid_out: Act or None (hidden
         state not written); img: Act view of the 3 image channels; alpha: (tensor pointer of image 0); tri: pointer or None;
-        sm: Act view (channels 16..23 of the Encoder_M input) or None."""
+        sm: Act view (channels 16..23 of the Encoder_M input) or None; fgr: (pointer of image 0, floats per image) = keep the
+        head's foreground estimate, planar [3][P] (otvm_conv2d_head_fgr), or None."""
         w = self.e.W[wname]
         assert x.C == w.I_pad and w.O == 16 and w.kh == 3
         out = hid_out if hid_out is not None else x
@@ -1298,6 +1362,10 @@ class FramePlan:
         self._keep += [p, h]
         flops = 2 * x.P * w.O * 9 * w.I * x.B
         abytes = 4 * (x.B * x.P * w.I + w.O * w.I * 9 + x.B * x.P * (16 if hid_out is not None else 0) + x.B * x.P * 4)
+        if fgr is not None:
+            S.append((self.lib.otvm_conv2d_head_fgr, (C.byref(p), C.byref(h), fgr[0], fgr[1]), "conv " + wname + " (+ head, F)", flops,
+                      abytes + 4 * x.B * x.P * 3, (x, hid_out if hid_out is not None else x)))
+            return p
         S.append((self.lib.otvm_conv2d_head, (C.byref(p), C.byref(h)), "conv " + wname + " (+ head)", flops, abytes,
                   (x, hid_out if hid_out is not None else x)))
         return p
@@ -1598,6 +1666,7 @@ class FramePlan:
         self.CLS_B = self.raws("cls", P, torch.uint8)
         self.ALPHA_P_B = self.raws("alpha_p", P)
         self.TRI_P_B = self.raws("tri_p", 3 * P)
+        self.FGR_P_B = self.raws("fgr_p", 3 * P) if self.fgr else None      # the refinement head's F, planar R, G, B (padded)
         self.enc_ws_B = self.raws("enc_ws", _rup(int(lib.otvm_trimap_encode_ws_bytes(Hp, Wp)), 256), torch.uint8)
         self.PROBS, self.CLS, self.ALPHA_P, self.TRI_P = self.PROBS_B[0], self.CLS_B[0], self.ALPHA_P_B[0], self.TRI_P_B[0]
 
@@ -1801,15 +1870,19 @@ class FramePlan:
             hid = SM.ch(0, 16)
             if fuse_head:
                 self.conv_head(S, h32, rf + "pred.2", hid, sd[rf + "pred.4.weight"], sd[rf + "pred.4.bias"], 10, img,
-                               self.ALPHA_P_B[0].data_ptr(), 1, P, tri=self.TRI_P_B[0].data_ptr(), sm=SM.ch(16, 8))
+                               self.ALPHA_P_B[0].data_ptr(), 1, P, tri=self.TRI_P_B[0].data_ptr(), sm=SM.ch(16, 8),
+                               fgr=(self.FGR_P_B[0].data_ptr(), 3 * P) if self.fgr else None)
                 self.steps["fba_tail%d" % par] = S
                 continue
             self.conv(S, h32, rf + "pred.2", hid, pad=1, act=LEAKY)
             for b in range(self.B):
-                S.append((lib.otvm_fba_head,
-                          (hid.img(b).ptr, hid.ld, sd[rf + "pred.4.weight"].data_ptr(), sd[rf + "pred.4.bias"].data_ptr(), 10,
-                           img.img(b).ptr, img.ld, P, self.ALPHA_P_B[b].data_ptr(), 1, self.TRI_P_B[b].data_ptr(),
-                           SM.ch(16, 8).img(b).ptr, SM.ld), "fba_head10"))
+                args = (hid.img(b).ptr, hid.ld, sd[rf + "pred.4.weight"].data_ptr(), sd[rf + "pred.4.bias"].data_ptr(), 10,
+                        img.img(b).ptr, img.ld, P, self.ALPHA_P_B[b].data_ptr(), 1, self.TRI_P_B[b].data_ptr(),
+                        SM.ch(16, 8).img(b).ptr, SM.ld)
+                if self.fgr:
+                    S.append((lib.otvm_fba_head_fgr, args + (self.FGR_P_B[b].data_ptr(),), "fba_head10 (+ F)"))
+                else:
+                    S.append((lib.otvm_fba_head, args, "fba_head10"))
             self.steps["fba_tail%d" % par] = S
 
         # ---------------- STM memorize (STM.py:201-228); key/value convs are bound to a slot at run time

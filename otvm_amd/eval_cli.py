@@ -9,6 +9,10 @@ Dataset layouts: otvm_amd/datasets.py (Demo_Test / VideoMatting108_Test, referen
 from the ground-truth alpha with the --trimap dilation, and SAD / MSE / dtSSD against the ground truth are
 accumulated on the device and reduced over ranks (--all-metrics: also Grad, Conn and SSDA).  Alpha PNGs are written as trunc(alpha*255) (eval.py:209-217);
 --viz adds the six-panel composite frames (eval.py:96-115) and, when ffmpeg exists, the mp4 (eval.py:229-242).
+--fgr writes the network's foreground estimate as straight-alpha RGBA PNGs, <out>/fgr/<seq>/<name>.png; --composite PATH|R,G,B
+writes that foreground over a new background (an image, resized once on the host to the clip's resolution, or a colour),
+<out>/comp/<seq>/<name>.png.  Both work for the demo and the VideoMatting108 layouts and with --gpus N; with --batch > 1 they
+are refused (as --viz is).
 Frame IO runs through otvm_amd/io_pipeline.py: the demo flow decodes ahead in a thread pool and uploads on a copy
 stream, both flows download the 8-bit alphas asynchronously and PNG-encode them in a pool (the reference's loop blocks
 on .cpu() + cv2.imwrite per frame, eval.py:209-217).
@@ -25,6 +29,21 @@ import os
 import torch
 
 
+def parse_composite(spec):
+    """--composite: "R,G,B" (0..255) -> ((r, g, b), None); anything else is the path of an image -> (None, path)."""
+    if spec is None:
+        return None, None
+    parts = spec.split(",")
+    if len(parts) == 3 and all(x.strip().isdigit() for x in parts):
+        c = tuple(int(x) for x in parts)
+        if any(x > 255 for x in c):
+            raise SystemExit("eval_cli: --composite colour components are 0..255, got %s" % spec)
+        return c, None
+    if not os.path.exists(spec):
+        raise SystemExit("eval_cli: --composite %s is neither R,G,B nor an existing image" % spec)
+    return None, spec
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--data", required=True)
@@ -32,6 +51,9 @@ def main(argv=None):
     ap.add_argument("--demo", action="store_true", help="demo layout; default: VideoMatting108 validation split")
     ap.add_argument("--subset", action="store_true", help="VideoMatting108: val_videos_subset.txt")
     ap.add_argument("--viz", action="store_true", help="also write the six-panel composites (eval.py --viz)")
+    ap.add_argument("--fgr", action="store_true", help="also write the foreground estimate as RGBA PNGs (<out>/fgr/<seq>/)")
+    ap.add_argument("--composite", default=None, metavar="PATH|R,G,B",
+                    help="also write the foreground composited over a new background image or colour (<out>/comp/<seq>/)")
     ap.add_argument("--max-frames", type=int, default=None, help="only the first N frames of every sequence")
     ap.add_argument("--weights", default=None)
     ap.add_argument("--synthetic-weights", action="store_true")
@@ -58,6 +80,8 @@ def main(argv=None):
     from .dist import run_sharded, self_launch_command
     from .io_pipeline import AlphaWriter, FramePrefetcher, _Listish
     from .video import run_video_matte
+
+    comp_color, comp_image = parse_composite(args.composite)
 
     if args.gpus is not None and args.gpus > 1 and "RANK" not in os.environ:
         import subprocess
@@ -115,7 +139,7 @@ def main(argv=None):
         args.batch = 1
         # (--viz and --sync-io are single-clip features -- matte_batch writes no viz frames and decodes every clip of a group up
         #  front -- so they keep batch 1 unless --batch is given explicitly)
-        if world > 1 and any(k is not None for k in keys) and not (args.viz or args.sync_io):
+        if world > 1 and any(k is not None for k in keys) and not (args.viz or args.sync_io or args.fgr or args.composite):
             def padded(k):
                 lw, uw, lh, uh = pad_amounts(k[0], k[1], 32)
                 return (k[0] + lh + uh) * (k[1] + lw + uw)
@@ -123,6 +147,9 @@ def main(argv=None):
     if args.batch > 1 and (args.viz or args.sync_io):
         raise SystemExit("eval_cli: --batch %d steps clips in lock-step through matte_batch, which implements neither --viz nor "
                          "--sync-io; drop one of them" % args.batch)
+    if args.batch > 1 and (args.fgr or args.composite):
+        raise SystemExit("eval_cli: --batch %d steps clips in lock-step through matte_batch, which implements neither --fgr nor "
+                         "--composite; drop one of them" % args.batch)
     if rank == 0:
         print("eval_cli: %d rank(s), lock-step batch %d per rank" % (world, args.batch))
     if distributed:
@@ -149,12 +176,35 @@ def main(argv=None):
         if args.viz:
             os.makedirs(vizdir, exist_ok=True)
         writer = None if args.sync_io else AlphaWriter(dev, outdir, [n + ".png" for n in data["names"]])
+        # foreground outputs: writers of their own (asynchronous also with --sync-io: only the alpha path mirrors eval.py's loop)
+        png_names = [n + ".png" for n in data["names"]]
+        want_fgr = args.fgr or args.composite is not None
+        fwriter = AlphaWriter(dev, os.path.join(args.out, "fgr", seq["name"]), png_names) if args.fgr else None
+        cwriter = AlphaWriter(dev, os.path.join(args.out, "comp", seq["name"]), png_names) if args.composite is not None else None
+        eng_of = model.module
+        bgr = not (demo and not args.sync_io)              # the prefetcher hands out RGB frames, the decoded arrays are BGR
+
+        def new_background():
+            if args.composite is None:
+                return None
+            if comp_image is None:
+                return comp_color[::-1] if bgr else comp_color
+            hw = resolution(seq)
+            if hw is None:
+                return None                                # an empty sequence: nothing to composite
+            import numpy as np
+            arr = np.asarray(Image.open(comp_image).convert("RGB").resize((hw[1], hw[0]), Image.BILINEAR))   # once per clip, on the host
+            return np.ascontiguousarray(arr[..., ::-1] if bgr else arr)
 
         def save(i, alpha, u8, out):
             if writer is None:
                 Image.fromarray(u8.cpu().numpy()).save(os.path.join(outdir, data["names"][i] + ".png"))
             else:
                 writer.put(i, u8)
+            if fwriter is not None:
+                fwriter.put(i, eng_of._engine.last_rgba_u8, bgr=bgr)
+            if cwriter is not None:
+                cwriter.put(i, eng_of._engine.last_comp_u8, bgr=bgr)
             if args.viz:
                 viz.write_viz_frame(os.path.join(vizdir, "f%d.jpg" % i), out)
         if demo:
@@ -164,16 +214,23 @@ def main(argv=None):
                 pre = FramePrefetcher(data["frame_paths"], dev)
                 frames, rgb = _Listish(pre), True
             res = run_video_matte(model, frames, trimap=data["trimap"], skip=args.skip, max_num=args.max_num,
-                                  on_frame=save, device=dev, frames_are_rgb=rgb, keep_on_device=True)
+                                  on_frame=save, device=dev, frames_are_rgb=rgb, keep_on_device=True,
+                                  foreground=want_fgr, new_background=new_background())
             if pre is not None:
                 pre.close()
         else:
             res = run_video_matte(model, data["frames"], alphas=data["alphas"], backgrounds=data["backgrounds"],
                                   skip=args.skip, max_num=args.max_num, on_frame=save, device=dev,
                                   gt_alpha_u8=data["gt_alpha_u8"], gt_mask="unknown", keep_on_device=True,
-                                  gt_image_metrics=args.all_metrics, gt_flow_metrics=args.messddt)
+                                  gt_image_metrics=args.all_metrics, gt_flow_metrics=args.messddt,
+                                  foreground=want_fgr, new_background=new_background())
         if writer is not None:
             writer.close()
+        for w in (fwriter, cwriter):
+            if w is not None:
+                w.close()
+        for k in ("fgr_u8", "comp_u8"):
+            res.pop(k, None)                       # written as PNGs; the per-clip results keep today's keys
         if args.viz:
             viz.make_viz_video(os.path.join(vizdir, "f%d.jpg"),                          # eval.py:229-242
                                os.path.join(args.out, "viz", "test", helpers.get_model_name(cfg), "viz",

@@ -74,7 +74,10 @@ class FramePrefetcher:
 
 
 class AlphaWriter:
-    """Asynchronous sink for 8-bit alphas: D2H on a copy stream into pinned memory, PNG encoding in a thread pool."""
+    """Asynchronous sink for 8-bit frames: D2H on a copy stream into pinned memory, PNG encoding in a thread pool.
+    Alphas [H,W] and, the same way (same pinned download, same pool, same back-pressure), the foreground outputs: RGBA
+    [H,W,4] and composites [H,W,3].  PIL wants R, G, B(, A): frames in B, G, R order (``put(..., bgr=True)``) are flipped on
+    the host, by the encoding thread, not on the device."""
 
     def __init__(self, device, outdir=None, names=None, workers=4, keep=False):
         self.dev = torch.device(device)
@@ -86,7 +89,7 @@ class AlphaWriter:
         self.futs = []
         self.encoded = {}
 
-    def put(self, i, u8):
+    def put(self, i, u8, bgr=False):
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(self.copy_stream):
@@ -96,12 +99,15 @@ class AlphaWriter:
             done = torch.cuda.Event()
             done.record(self.copy_stream)
         u8.record_stream(self.copy_stream)
-        self.futs.append(self.pool.submit(self._encode, i, host, done))
+        self.futs.append(self.pool.submit(self._encode, i, host, done, bgr))
 
-    def _encode(self, i, host, done):
+    def _encode(self, i, host, done, bgr=False):
         from PIL import Image
         done.synchronize()
-        im = Image.fromarray(host.numpy())
+        arr = host.numpy()
+        if bgr and arr.ndim == 3:
+            arr = np.ascontiguousarray(arr[..., [2, 1, 0] + list(range(3, arr.shape[-1]))])
+        im = Image.fromarray(arr)
         if self.outdir:
             name = self.names[i] if self.names else "%05d.png" % i
             im.save(os.path.join(self.outdir, name), compress_level=1)

@@ -76,6 +76,11 @@ class PreprocessParams(C.Structure):
                 ("fg_u8", vp), ("bg_u8", vp), ("u8_rgb", i32)]
 
 
+class FgrParams(C.Structure):
+    _fields_ = [("alpha_p", vp), ("fgr_p", vp), ("Hp", i32), ("Wp", i32), ("H", i32), ("W", i32), ("lh", i32), ("lw", i32),
+                ("fgr", vp), ("rgba_u8", vp), ("comp_u8", vp), ("bg_u8", vp), ("bg_color", C.c_ubyte * 3), ("u8_rgb", i32)]
+
+
 class PpmHeadParams(C.Structure):
     _fields_ = [("pooled", vp), ("C", i32), ("K_pad", i32), ("Cout", i32),
                 ("w", vp * 4), ("bias", vp * 4), ("gamma", vp * 4), ("beta", vp * 4), ("out", vp * 4),
@@ -100,6 +105,7 @@ _PROTOS = {
     "otvm_conv2d_input_norm_kind": (i32, [C.POINTER(ConvParams)]),
     "otvm_conv2d_accepts_input_residual": (i32, [C.POINTER(ConvParams)]),
     "otvm_conv2d_head": (i32, [C.POINTER(ConvParams), C.POINTER(HeadParams), vp]),
+    "otvm_conv2d_head_fgr": (i32, [C.POINTER(ConvParams), C.POINTER(HeadParams), vp, i64, vp]),
     "otvm_head16_weight_bytes_f16x3": (i64, []),
     "otvm_pack_head16_weight_f16x3": (i32, [vp, i32, i32, i32, vp, vp, vp]),
     "otvm_conv2d_candidates": (i32, [C.POINTER(ConvParams), C.POINTER(i32), i32]),
@@ -126,6 +132,8 @@ _PROTOS = {
     "otvm_trimap_encode_ws_bytes": (i64, [i32, i32]),
     "otvm_trimap_encode": (i32, [vp, i32, i32, vp, vp, vp, i32, vp, i32, vp, vp]),
     "otvm_fba_head": (i32, [vp, i32, vp, vp, i32, vp, i32, i64, vp, i32, vp, vp, i32, vp]),
+    "otvm_fba_head_fgr": (i32, [vp, i32, vp, vp, i32, vp, i32, i64, vp, i32, vp, vp, i32, vp, vp]),
+    "otvm_fgr_outputs": (i32, [C.POINTER(FgrParams), vp]),
     "otvm_crop_outputs": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "otvm_trimap_from_alpha": (i32, [vp, i32, i32, i32, vp, vp, vp]),
     "otvm_onehot_argmax3": (i32, [vp, i64, vp, vp]),

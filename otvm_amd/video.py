@@ -4,6 +4,8 @@
 BASELINE.json names a ``run_video_matte()`` call surface; the reference has no such function (its loop
 is inlined in eval.py), so this reproduces that loop around the reference-shaped ``EvalModel``.
 """
+import contextlib
+
 import numpy as np
 import torch
 
@@ -45,9 +47,42 @@ def _as_tensor(x):
     return torch.from_numpy(a if a.flags.writeable else a.copy())
 
 
+def _background_at(spec, i, dev, cache):
+    """Entry ``i`` of a ``new_background``: a TUPLE is a colour triple and an array / tensor [H,W,3] one image, either serving
+    every frame; a LIST (or a [T,H,W,3] array) holds one of those per frame.  An image that serves every frame is uploaded once."""
+    per_frame = isinstance(spec, list) or (hasattr(spec, "ndim") and spec.ndim == 4)
+    x = spec[i] if per_frame else spec
+    if isinstance(x, tuple):
+        return x
+    if not per_frame and "image" in cache:
+        return cache["image"]
+    t = _as_tensor(x)
+    if t.dtype != torch.uint8:
+        raise ValueError("run_video_matte: a new background image is uint8 [H,W,3], got %s" % t.dtype)
+    t = t.to(dev).contiguous()
+    if not per_frame:
+        cache["image"] = t
+    return t
+
+
+@contextlib.contextmanager
+def _foreground_option(core, on):
+    """EvalModel.foreground = True for the clip (when asked for); the model's option and background are restored afterwards."""
+    if not on:
+        yield
+        return
+    saved = (core.foreground, core._background)
+    core.foreground = True
+    try:
+        yield
+    finally:
+        core.foreground, core._background = saved
+
+
 def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, skip=10, max_num=5,
                     frames_are_rgb=False, on_frame=None, device=None, keep_on_device=False, gt_alpha_u8=None,
-                    gt_mask_u8=None, gt_mask=None, gt_image_metrics=False, gt_flow_metrics=False):
+                    gt_mask_u8=None, gt_mask=None, gt_image_metrics=False, gt_flow_metrics=False, foreground=False,
+                    new_background=None):
     """Matte one sequence.
 
     model       : EvalModel (optionally wrapped in nn.DataParallel), on the GPU
@@ -62,6 +97,11 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                   (ClipMetrics(flow_metrics=True))
     backgrounds : optional per-frame BG images (V108 composites fg*a + bg*(1-a)), same dtype / channel order as the
                   frames; default bg = fg
+    foreground  : also return the network's foreground estimate as straight-alpha RGBA: "fgr_u8" [T,H,W,4] uint8, colour in
+                  the frames' channel order, A = alpha_u8 (EvalModel.foreground; the model's option is restored afterwards)
+    new_background : composite that foreground over a new background -> "comp_u8" [T,H,W,3].  A tuple (c0, c1, c2) is a
+                  colour, a uint8 [H,W,3] array / tensor an image of the frames' resolution, a list one of those per frame;
+                  all in the frames' channel order (switches ``foreground`` on: the composite needs F)
     Returns dict(alpha=[T,H,W] float32, alpha_u8=[T,H,W] uint8 (truncated, eval.py:209), trimap=[T,3,H,W],
     bank_frames=[per frame: ids of the frames resident in the memory bank after that frame's update]).
     """
@@ -69,7 +109,9 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
     T = len(frames)
     dev = device or next(model.parameters()).device
     out_a, out_u8, out_t, bank_log = [], [], [], []
+    out_f, out_c, bg_cache = [], [], {}
     core = model.module if hasattr(model, "module") else model
+    foreground = bool(foreground) or new_background is not None
     metrics = (ClipMetrics(dev, image_metrics=gt_image_metrics, flow_metrics=gt_flow_metrics) if gt_alpha_u8 is not None
                else None)
     # loop invariants: the user trimap (25 MB as fp32 at 1080p) is uploaded once, not once per frame; the dummy alpha
@@ -79,73 +121,85 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
         t = _as_tensor(trimap)
         tri_dev = t.to(dev).float()[None, None]
     ones = None
-    for i in range(T):
-        f = _as_tensor(frames[i])
-        b = _as_tensor(backgrounds[i]) if backgrounds is not None else None
-        extra = {}
-        if f.dtype == torch.uint8 and (b is None or b.dtype == torch.uint8):
-            # decoded images go to the device as they are ([H,W,3] uint8): the preprocess kernel converts, flips the
-            # channel order and composites -- no per-frame torch conversion / transposition kernels
-            ready = getattr(f, "_otvm_ready", None)           # upload event of the IO pipeline's prefetcher
-            fg = f.to(dev, non_blocking=True)
-            bg = fg if b is None else b.to(dev, non_blocking=True)
-            if b is not None and getattr(b, "_otvm_ready", None) is not None:
-                torch.cuda.current_stream(dev).wait_event(b._otvm_ready)
-            H, W = fg.shape[:2]
-            extra["_frames_rgb"] = bool(frames_are_rgb)
-            if ready is not None:
-                # the upload event may only travel to the model (whose query-encoder stream then starts on it, ahead of the
-                # launch stream) when EVERYTHING the preprocess reads is covered by it or loop-invariant: the frame itself
-                # (no copy made here), no separately uploaded background, and the trimap flow's constant alpha -- a per-frame
-                # alpha is written by the launch stream just below.  Otherwise the launch stream waits for the upload
-                # and the model orders its side streams behind the launch stream.
-                if b is None and fg is f and trimap is not None:
-                    extra["_inputs_ready"] = ready
-                else:
-                    torch.cuda.current_stream(dev).wait_event(ready)
-        else:
-            f = f.to(dev).float()
-            if frames_are_rgb:
-                f = f.flip(-1)
-            fg = f.permute(2, 0, 1)[None, None].contiguous()
-            H, W = fg.shape[-2:]
-            if b is not None:                                 # backgrounds come in the same channel order as the frames
-                b = b.to(dev).float()
-                if frames_are_rgb:
-                    b = b.flip(-1)
-                bg = b.permute(2, 0, 1)[None, None].contiguous()
+    with _foreground_option(core, foreground):
+        for i in range(T):
+            f = _as_tensor(frames[i])
+            b = _as_tensor(backgrounds[i]) if backgrounds is not None else None
+            extra = {}
+            if f.dtype == torch.uint8 and (b is None or b.dtype == torch.uint8):
+                # decoded images go to the device as they are ([H,W,3] uint8): the preprocess kernel converts, flips the
+                # channel order and composites -- no per-frame torch conversion / transposition kernels
+                ready = getattr(f, "_otvm_ready", None)           # upload event of the IO pipeline's prefetcher
+                fg = f.to(dev, non_blocking=True)
+                bg = fg if b is None else b.to(dev, non_blocking=True)
+                if b is not None and getattr(b, "_otvm_ready", None) is not None:
+                    torch.cuda.current_stream(dev).wait_event(b._otvm_ready)
+                H, W = fg.shape[:2]
+                extra["_frames_rgb"] = bool(frames_are_rgb)
+                if ready is not None:
+                    # the upload event may only travel to the model (whose query-encoder stream then starts on it, ahead of the
+                    # launch stream) when EVERYTHING the preprocess reads is covered by it or loop-invariant: the frame itself
+                    # (no copy made here), no separately uploaded background, and the trimap flow's constant alpha -- a per-frame
+                    # alpha is written by the launch stream just below.  Otherwise the launch stream waits for the upload
+                    # and the model orders its side streams behind the launch stream.
+                    if b is None and fg is f and trimap is not None:
+                        extra["_inputs_ready"] = ready
+                    else:
+                        torch.cuda.current_stream(dev).wait_event(ready)
             else:
-                bg = fg
-        if trimap is not None:
-            if ones is None or ones.shape[-2:] != (H, W):
-                ones = torch.ones(1, 1, 1, H, W, device=dev)
-            a, tri_gt = ones, tri_dev
-        else:
-            al = alphas[i]
-            al = _as_tensor(al)
-            a = al.to(dev).float()[None, None, None]
-            tri_gt = None
-        memorize, max_memory_num, large = memory_schedule(i, H, W, skip, max_num)
-        out = model(a, fg, bg, tri=None, tri_gt=tri_gt, first_frame=(i == 0), last_frame=(i == T - 1),
-                    memorize=memorize, max_memory_num=max_memory_num, large_input=large, **extra)
-        alpha = out[3][0, 0, 0]
-        u8 = core._engine.last_alpha_u8
-        bank_log.append(list(core.memories["frames"]))          # frame ids resident after this frame's update (host list)
-        if metrics is not None:
-            g = gt_alpha_u8[i]
-            g = _as_tensor(g)
-            mk = gt_mask
-            if gt_mask_u8 is not None:
-                mk = gt_mask_u8[i]
-                mk = (_as_tensor(mk)).to(dev)
-            metrics.add(u8, g.to(dev), mk)
-        if on_frame is not None:
-            on_frame(i, alpha, u8, out)
-        if keep_on_device:
-            out_a.append(alpha), out_u8.append(u8), out_t.append(out[1][0, 0])
-        else:
-            out_a.append(alpha.cpu()), out_u8.append(u8.cpu()), out_t.append(out[1][0, 0].cpu())
+                f = f.to(dev).float()
+                if frames_are_rgb:
+                    f = f.flip(-1)
+                fg = f.permute(2, 0, 1)[None, None].contiguous()
+                H, W = fg.shape[-2:]
+                if b is not None:                                 # backgrounds come in the same channel order as the frames
+                    b = b.to(dev).float()
+                    if frames_are_rgb:
+                        b = b.flip(-1)
+                    bg = b.permute(2, 0, 1)[None, None].contiguous()
+                else:
+                    bg = fg
+            if trimap is not None:
+                if ones is None or ones.shape[-2:] != (H, W):
+                    ones = torch.ones(1, 1, 1, H, W, device=dev)
+                a, tri_gt = ones, tri_dev
+            else:
+                al = alphas[i]
+                al = _as_tensor(al)
+                a = al.to(dev).float()[None, None, None]
+                tri_gt = None
+            memorize, max_memory_num, large = memory_schedule(i, H, W, skip, max_num)
+            if foreground:
+                core.set_background(None if new_background is None else _background_at(new_background, i, dev, bg_cache))
+            out = model(a, fg, bg, tri=None, tri_gt=tri_gt, first_frame=(i == 0), last_frame=(i == T - 1),
+                        memorize=memorize, max_memory_num=max_memory_num, large_input=large, **extra)
+            alpha = out[3][0, 0, 0]
+            u8 = core._engine.last_alpha_u8
+            bank_log.append(list(core.memories["frames"]))          # frame ids resident after this frame's update (host list)
+            if metrics is not None:
+                g = gt_alpha_u8[i]
+                g = _as_tensor(g)
+                mk = gt_mask
+                if gt_mask_u8 is not None:
+                    mk = gt_mask_u8[i]
+                    mk = (_as_tensor(mk)).to(dev)
+                metrics.add(u8, g.to(dev), mk)
+            if on_frame is not None:
+                on_frame(i, alpha, u8, out)
+            if keep_on_device:
+                out_a.append(alpha), out_u8.append(u8), out_t.append(out[1][0, 0])
+            else:
+                out_a.append(alpha.cpu()), out_u8.append(u8.cpu()), out_t.append(out[1][0, 0].cpu())
+            if foreground:
+                eng = core._engine
+                out_f.append(eng.last_rgba_u8 if keep_on_device else eng.last_rgba_u8.cpu())
+                if new_background is not None:
+                    out_c.append(eng.last_comp_u8 if keep_on_device else eng.last_comp_u8.cpu())
     res = dict(alpha=torch.stack(out_a), alpha_u8=torch.stack(out_u8), trimap=torch.stack(out_t), bank_frames=bank_log)
+    if foreground:
+        res["fgr_u8"] = torch.stack(out_f)
+        if new_background is not None:
+            res["comp_u8"] = torch.stack(out_c)
     if metrics is not None:
         res["metrics"] = metrics.result()
     return res
@@ -153,7 +207,7 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
 
 def run_video_matte_batch(model, clips, trimaps=None, alphas=None, backgrounds=None, skip=10, max_num=5, frames_are_rgb=False,
                           device=None, keep_on_device=False, on_frame=None, gt_alpha_u8=None, gt_mask=None,
-                          gt_image_metrics=False, gt_flow_metrics=False):
+                          gt_image_metrics=False, gt_flow_metrics=False, foreground=False, new_background=None):
     """Matte B sequences of one resolution in LOCK-STEP (round 3): frame i of every clip goes through the network in one
     batched step (EvalModel.forward_batch: one launch per layer over the B images, per-sequence memory banks).
     clips: list of B frame arrays ([T_b,H,W,3] uint8 / float, BGR unless frames_are_rgb); trimaps: list of B first-frame
@@ -168,7 +222,9 @@ def run_video_matte_batch(model, clips, trimaps=None, alphas=None, backgrounds=N
     same kernel configurations).  bank_frames follows the SHARED schedule: ``last_frame`` is keyed to the longest clip, so a
     shorter clip's final entry still lists the frame whose memorize is pending -- the stand-alone run, whose last frame
     memorises nothing, does not (the one documented difference).
-    Returns a list of B dicts (alpha, alpha_u8, trimap, bank_frames[, metrics])."""
+    foreground / new_background: as run_video_matte ("fgr_u8" [T_b,H,W,4], "comp_u8" [T_b,H,W,3] per clip); new_background = a
+    list of B entries, one per clip, each what run_video_matte takes (colour tuple, image, or per-frame list).
+    Returns a list of B dicts (alpha, alpha_u8, trimap, bank_frames[, metrics][, fgr_u8][, comp_u8])."""
     B = len(clips)
     lens = [len(c) for c in clips]
     T = max(lens)
@@ -176,74 +232,91 @@ def run_video_matte_batch(model, clips, trimaps=None, alphas=None, backgrounds=N
         raise ValueError("run_video_matte_batch: give either trimaps (demo flow) or alphas (VideoMatting108 flow)")
     core = model.module if hasattr(model, "module") else model
     dev = device or next(core.parameters()).device
-    res = [dict(alpha=[], alpha_u8=[], trimap=[], bank_frames=[]) for _ in range(B)]
+    res = [dict(alpha=[], alpha_u8=[], trimap=[], bank_frames=[], fgr_u8=[], comp_u8=[]) for _ in range(B)]
+    foreground = bool(foreground) or new_background is not None
+    if new_background is not None and not (isinstance(new_background, list) and len(new_background) == B):
+        raise ValueError("run_video_matte_batch: new_background is a list of one entry per clip")
+    bg_cache = [{} for _ in range(B)]
     metrics = ([ClipMetrics(dev, image_metrics=gt_image_metrics, flow_metrics=gt_flow_metrics) for _ in range(B)]
                if gt_alpha_u8 is not None else None)
     tri_dev = None if trimaps is None else [_as_tensor(t).to(dev).float()[None, None] for t in trimaps]
     ones = None
-    for i in range(T):
-        A, FG, BG = [], [], []
-        for b in range(B):
-            j = min(i, lens[b] - 1)                               # a clip that has ended repeats its last frame (discarded)
-            f = _as_tensor(clips[b][j])
-            bk = _as_tensor(backgrounds[b][j]) if backgrounds is not None else None
-            if f.dtype == torch.uint8 and (bk is None or bk.dtype == torch.uint8):
-                fg = f.to(dev, non_blocking=True)
-                bg = fg if bk is None else bk.to(dev, non_blocking=True)
-                # frames handed over by the IO pipeline's prefetcher carry their upload event: the launch stream waits for
-                # it before anything reads them (as run_video_matte does; the batched step makes no promise to the engine
-                # about its inputs, so its side streams order themselves behind the launch stream)
-                for src in (f, bk):
-                    ev = getattr(src, "_otvm_ready", None) if src is not None else None
-                    if ev is not None:
-                        torch.cuda.current_stream(dev).wait_event(ev)
-                H, W = fg.shape[:2]
-                rgb = bool(frames_are_rgb)
-            else:
-                f = f.to(dev).float()
-                if frames_are_rgb:
-                    f = f.flip(-1)
-                fg = f.permute(2, 0, 1)[None, None].contiguous()
-                H, W = fg.shape[-2:]
-                if bk is not None:
-                    bk = bk.to(dev).float()
-                    if frames_are_rgb:
-                        bk = bk.flip(-1)
-                    bg = bk.permute(2, 0, 1)[None, None].contiguous()
+    with _foreground_option(core, foreground):
+        for i in range(T):
+            A, FG, BG = [], [], []
+            for b in range(B):
+                j = min(i, lens[b] - 1)                               # a clip that has ended repeats its last frame (discarded)
+                f = _as_tensor(clips[b][j])
+                bk = _as_tensor(backgrounds[b][j]) if backgrounds is not None else None
+                if f.dtype == torch.uint8 and (bk is None or bk.dtype == torch.uint8):
+                    fg = f.to(dev, non_blocking=True)
+                    bg = fg if bk is None else bk.to(dev, non_blocking=True)
+                    # frames handed over by the IO pipeline's prefetcher carry their upload event: the launch stream waits for
+                    # it before anything reads them (as run_video_matte does; the batched step makes no promise to the engine
+                    # about its inputs, so its side streams order themselves behind the launch stream)
+                    for src in (f, bk):
+                        ev = getattr(src, "_otvm_ready", None) if src is not None else None
+                        if ev is not None:
+                            torch.cuda.current_stream(dev).wait_event(ev)
+                    H, W = fg.shape[:2]
+                    rgb = bool(frames_are_rgb)
                 else:
-                    bg = fg
-                rgb = False
-            if trimaps is not None:
-                if ones is None or ones.shape[-2:] != (H, W):
-                    ones = torch.ones(1, 1, 1, H, W, device=dev)
-                a = ones
-            else:
-                a = _as_tensor(alphas[b][j]).to(dev).float()[None, None, None]
-            A.append(a), FG.append(fg), BG.append(bg)
-        memorize, max_memory_num, large = memory_schedule(i, H, W, skip, max_num)
-        outs = core.forward_batch(A, FG, BG, tri_dev if tri_dev is not None else [None] * B, first_frame=(i == 0),
-                                  last_frame=(i == T - 1), memorize=memorize, max_memory_num=max_memory_num, large_input=large,
-                                  _frames_rgb=rgb)
-        u8s = core._engine.last_alpha_u8_b
-        bank = list(core.memories["frames"])
-        for b in range(B):
-            if i >= lens[b]:
-                continue
-            al, u8, tr = outs[b][3][0, 0, 0], u8s[b], outs[b][1][0, 0]
-            if metrics is not None:
-                metrics[b].add(u8, _as_tensor(gt_alpha_u8[b][i]).to(dev), gt_mask)
-            if on_frame is not None:
-                on_frame(b, i, al, u8, outs[b])
-            if not keep_on_device:
-                al, u8, tr = al.cpu(), u8.cpu(), tr.cpu()
-            res[b]["alpha"].append(al), res[b]["alpha_u8"].append(u8), res[b]["trimap"].append(tr)
-            res[b]["bank_frames"].append(bank)
+                    f = f.to(dev).float()
+                    if frames_are_rgb:
+                        f = f.flip(-1)
+                    fg = f.permute(2, 0, 1)[None, None].contiguous()
+                    H, W = fg.shape[-2:]
+                    if bk is not None:
+                        bk = bk.to(dev).float()
+                        if frames_are_rgb:
+                            bk = bk.flip(-1)
+                        bg = bk.permute(2, 0, 1)[None, None].contiguous()
+                    else:
+                        bg = fg
+                    rgb = False
+                if trimaps is not None:
+                    if ones is None or ones.shape[-2:] != (H, W):
+                        ones = torch.ones(1, 1, 1, H, W, device=dev)
+                    a = ones
+                else:
+                    a = _as_tensor(alphas[b][j]).to(dev).float()[None, None, None]
+                A.append(a), FG.append(fg), BG.append(bg)
+            memorize, max_memory_num, large = memory_schedule(i, H, W, skip, max_num)
+            if foreground:
+                core.set_background(None if new_background is None else
+                                    [_background_at(new_background[b], min(i, lens[b] - 1), dev, bg_cache[b]) for b in range(B)])
+            outs = core.forward_batch(A, FG, BG, tri_dev if tri_dev is not None else [None] * B, first_frame=(i == 0),
+                                      last_frame=(i == T - 1), memorize=memorize, max_memory_num=max_memory_num, large_input=large,
+                                      _frames_rgb=rgb)
+            u8s = core._engine.last_alpha_u8_b
+            bank = list(core.memories["frames"])
+            for b in range(B):
+                if i >= lens[b]:
+                    continue
+                al, u8, tr = outs[b][3][0, 0, 0], u8s[b], outs[b][1][0, 0]
+                if metrics is not None:
+                    metrics[b].add(u8, _as_tensor(gt_alpha_u8[b][i]).to(dev), gt_mask)
+                if on_frame is not None:
+                    on_frame(b, i, al, u8, outs[b])
+                if not keep_on_device:
+                    al, u8, tr = al.cpu(), u8.cpu(), tr.cpu()
+                res[b]["alpha"].append(al), res[b]["alpha_u8"].append(u8), res[b]["trimap"].append(tr)
+                res[b]["bank_frames"].append(bank)
+                if foreground:
+                    eng = core._engine
+                    res[b]["fgr_u8"].append(eng.last_rgba_u8_b[b] if keep_on_device else eng.last_rgba_u8_b[b].cpu())
+                    if new_background is not None:
+                        res[b]["comp_u8"].append(eng.last_comp_u8_b[b] if keep_on_device else eng.last_comp_u8_b[b].cpu())
     out = []
     for b, r in enumerate(res):
         d = dict(alpha=torch.stack(r["alpha"]), alpha_u8=torch.stack(r["alpha_u8"]), trimap=torch.stack(r["trimap"]),
                  bank_frames=r["bank_frames"])
         if metrics is not None:
             d["metrics"] = metrics[b].result()
+        if foreground:
+            d["fgr_u8"] = torch.stack(r["fgr_u8"])
+            if new_background is not None:
+                d["comp_u8"] = torch.stack(r["comp_u8"])
         out.append(d)
     return out
 
