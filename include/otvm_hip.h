@@ -64,7 +64,8 @@ const char* otvm_last_error(void);
                                  21: otvm_optflow_farneback / _ws_bytes / _params, otvm_matting_messddt (MESSDdt);
                                  (21, additive: the foreground outputs -- the entry points with _fgr in their names and the output
                                   kernel of otvm_fgr_params are NEW symbols only; no existing struct, prototype or result changed, so a
-                                  caller built against the earlier 21 runs unchanged and the number stays) */
+                                  caller built against the earlier 21 runs unchanged and the number stays;
+                                  likewise otvm_trimap_apply_labels, the label pass of the keyframe corrections) */
 int otvm_abi_version(void);
 
 /* ---------------------------------------------------------------- weights (load time) ----------
@@ -421,6 +422,14 @@ int otvm_pad_trimap(const float* tri, int H, int W, float* out, int Hp, int Wp, 
 /* STM decoder tail: x4 bilinear upsample of the [h4*w4,3] logits (ld) + softmax over the 3 classes
  * -> planar probs [3,Hp,Wp] (STM.py:136, alpha/model.py:440) */
 int otvm_upsample4_softmax3(const float* logits, int h4, int w4, int ld, float* probs, void* stream);
+
+/* User labels over the propagated trimap, between the STM decoder's softmax and the encoding (an extension of
+ * alpha/model.py:425-443, where the reference takes a trimap on the first frame only and feeds every later frame the
+ * propagated softmax as it is): wherever labels[y][x] is a class -- 0 bg, 1 unknown, 2 fg -- the three planes of
+ * probs [3,Hp,Wp] at (lh + y, lw + x) become that class's exact one-hot (1.f / 0.f).  Every other label value (255 =
+ * unlabelled by convention) and the padding border keep the bits they hold.  labels: uint8 [H,W].  One pass, 16-byte
+ * stores (probs 16-byte aligned, Wp % 4 == 0); a group of four pixels without a label costs its four label bytes.       */
+int otvm_trimap_apply_labels(float* probs, const uint8_t* labels, int H, int W, int Hp, int Wp, int lh, int lw, void* stream);
 
 /* 8-channel trimap encoding (alpha/model.py:40-53, utils/utils.py:12-39): argmax class map, exact
  * Euclidean distance transform of the bg / fg classes on device (integer d^2), three Gaussians each,

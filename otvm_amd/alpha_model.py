@@ -77,36 +77,52 @@ class EvalModel(nn.Module):
 
     @property
     def memories(self):
-        """Bank introspection (reference: self.memories['key'].shape[3] slots)."""
+        """Bank introspection (reference: self.memories['key'].shape[3] slots): the frame ids resident, and those of them
+        that are anchors (frames that were given a trimap: the first frame, keyframes)."""
         eng = self._engine
         if eng is None:
-            return {"frames": []}
-        return {"frames": eng.bank_frames()}
+            return {"frames": [], "anchors": []}
+        return {"frames": eng.bank_frames(), "anchors": eng.bank_anchors()}
+
+    def drop_non_anchors(self):
+        """Keep only the anchor slots of the memory bank (video.run_video_matte: before the backward sweep of a keyframe clip)."""
+        if self._engine is not None:
+            self._engine.drop_non_anchors()
 
     @torch.no_grad()
     def forward(self, a, fg, bg, tri=None, tri_gt=None, first_frame=False, last_frame=False, memorize=False,
-                max_memory_num=2, large_input=False, _frame_id=None, _cls_override=None, _frames_rgb=False,
-                _inputs_ready=None):
+                max_memory_num=2, large_input=False, keyframe=False, labels=None, _frame_id=None, _cls_override=None,
+                _frames_rgb=False, _inputs_ready=None):
+        """Extensions behind the reference's arguments (defaults = the reference's frame step):
+        keyframe=True with ``tri_gt`` on a later frame: the frame runs on that trimap as a first frame does -- no propagation, no
+        memory read -- WITHOUT resetting the bank, and is memorised as an anchor slot, which the bank policy never evicts;
+        labels = uint8 [H,W] (0 bg, 1 unknown, 2 fg, 255 unlabelled) on a later frame: the propagated trimap is overwritten with
+        the exact one-hot of the label wherever there is one (keyframe=True then only makes the slot an anchor).
+        Both need max_memory_num >= 2; neither exists for forward_batch."""
         if tri is not None:
-            # alpha/model.py:395-396: unreachable from eval.py (EvalDataset is built with trimap=None, eval.py:133)
-            raise NotImplementedError("per-frame `tri` input is not part of the reference eval path")
+            # alpha/model.py:395-396: unreachable from eval.py (EvalDataset is built with trimap=None, eval.py:133); a trimap for
+            # a later frame goes through tri_gt with keyframe=True
+            raise NotImplementedError("per-frame `tri` input is not part of the reference eval path (a later frame's trimap: "
+                                      "tri_gt with keyframe=True)")
         eng = self._get_engine()
         self._push_options(eng)
         out = eng.frame(a, fg, bg, tri_gt=tri_gt, first_frame=bool(first_frame), last_frame=bool(last_frame),
                         memorize=bool(memorize), max_memory_num=int(max_memory_num),
                         dilate_kernel=self.DILATION_KERNEL, frame_id=_frame_id, cls_override=_cls_override,
-                        frames_rgb=bool(_frames_rgb), inputs_ready=_inputs_ready)
+                        frames_rgb=bool(_frames_rgb), inputs_ready=_inputs_ready, keyframe=bool(keyframe), labels=labels)
         self.memory_update = memorize
         return out
 
     @torch.no_grad()
     def forward_batch(self, a, fg, bg, tri_gt, first_frame=False, last_frame=False, memorize=False, max_memory_num=2,
-                      large_input=False, _frames_rgb=False, _inputs_ready=None, _cls_override=None):
+                      large_input=False, _frames_rgb=False, _inputs_ready=None, _cls_override=None, keyframe=False, labels=None):
         """Round 3 extension (not part of the reference surface): the same frame step for B independent sequences stepped in
         LOCK-STEP -- ``a``, ``fg``, ``bg``, ``tri_gt`` are lists of B per-sequence inputs shaped as ``forward`` takes them
         (one resolution, one memory schedule; every sequence keeps its own memory bank).  Every layer runs as one launch
         over the B images, which fills the chip on the small maps a single sequence leaves mostly idle.  Returns a list of
         B 5-tuples; each equals what ``forward`` returns for that sequence run alone with the same kernel configurations."""
+        if keyframe or labels is not None:
+            raise NotImplementedError("otvm_amd: keyframe / labels are single-sequence options of forward()")
         eng = self._get_engine()
         self._push_options(eng)
         out = eng.frame_batch(list(a), list(fg), list(bg), list(tri_gt), first_frame=bool(first_frame), last_frame=bool(last_frame),

@@ -188,6 +188,41 @@ __global__ void onehot_argmax3_kernel(const float* __restrict__ tri, int64_t P, 
     }
 }
 
+// User labels over the propagated trimap (include/otvm_hip.h: otvm_trimap_apply_labels).  One thread owns four consecutive
+// pixels of a padded row (Wp % 4 == 0: a 16-byte group never straddles rows): it reads their four label bytes -- 255 for the
+// padding border -- and, only when one of them carries a class, rewrites that group of the three planes with 16-byte stores,
+// labelled lanes as the exact one-hot, the others with the value they held.  An unlabelled group costs its label bytes alone.
+__global__ void trimap_apply_labels_kernel(float* __restrict__ probs, const uint8_t* __restrict__ labels, int H, int W, int Hp,
+                                           int Wp, int lh, int lw) {
+    const int Wq = Wp >> 2;
+    const int64_t P = (int64_t)Hp * Wp, G = (int64_t)Hp * Wq;
+    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < G; g += (int64_t)gridDim.x * blockDim.x) {
+        const int yp = (int)(g / Wq), xp = (int)(g - (int64_t)yp * Wq) * 4;
+        const int y = yp - lh;
+        if ((unsigned)y >= (unsigned)H) continue;             // a padding row
+        const uint8_t* row = labels + (int64_t)y * W;
+        int l[4];
+        bool any = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int x = xp + j - lw;
+            const int v = (unsigned)x < (unsigned)W ? (int)row[x] : 255;
+            l[j] = v <= 2 ? v : -1;                           // 0 / 1 / 2 = a class; everything else leaves the pixel alone
+            any = any || l[j] >= 0;
+        }
+        if (!any) continue;
+        const int64_t i = (int64_t)yp * Wp + xp;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            f32x4* q = reinterpret_cast<f32x4*>(probs + c * P + i);
+            f32x4 v = *q;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = l[j] < 0 ? v[j] : (l[j] == c ? 1.f : 0.f);
+            *q = v;
+        }
+    }
+}
+
 int grid_for(int64_t total) {
     int64_t b = (total + 255) / 256;
     return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
@@ -210,6 +245,20 @@ extern "C" int otvm_pad_trimap(const float* tri, int H, int W, float* out, int H
     hipLaunchKernelGGL(pad_trimap_kernel, dim3(grid_for((int64_t)Hp * Wp)), dim3(256), 0, (hipStream_t)stream, tri, H, W, out,
                        Hp, Wp, lh, lw);
     OTVM_CHECK_LAUNCH("otvm_pad_trimap");
+    return 0;
+}
+
+extern "C" int otvm_trimap_apply_labels(float* probs, const uint8_t* labels, int H, int W, int Hp, int Wp, int lh, int lw,
+                                        void* stream) {
+    OTVM_REQUIRE(probs && labels && H > 0 && W > 0, "otvm_trimap_apply_labels: null pointer or empty label map");
+    OTVM_REQUIRE(lh >= 0 && lw >= 0 && (int64_t)lh + H <= Hp && (int64_t)lw + W <= Wp,
+                 "otvm_trimap_apply_labels: a %dx%d label map at (%d, %d) does not lie inside the %dx%d padded frame", W, H, lw, lh,
+                 Wp, Hp);
+    OTVM_REQUIRE(Wp % 4 == 0 && ((uintptr_t)probs & 15) == 0,
+                 "otvm_trimap_apply_labels: probs must be 16-byte aligned with a padded width that is a multiple of 4");
+    hipLaunchKernelGGL(trimap_apply_labels_kernel, dim3(grid_for((int64_t)Hp * (Wp / 4))), dim3(256), 0, (hipStream_t)stream, probs,
+                       labels, H, W, Hp, Wp, lh, lw);
+    OTVM_CHECK_LAUNCH("otvm_trimap_apply_labels");
     return 0;
 }
 

@@ -6,7 +6,10 @@ Mirrors the iteration protocol of the reference so a loop written against it kee
     for data_name, data_root, FG, BG, a, tri, seq_name in VideoMatting108_Test(root): # dataset.py:959-1017
 
     demo  : <root>/<seq>/frames/*  and  <root>/<seq>/trimap/<frame stem>.png  (the most recent existing trimap
-            path is repeated for later frames; '' before the first one)
+            path is repeated for later frames; '' before the first one).  The reference's model consumes the first
+            frame's trimap only; load_sequence(keyframes=True) also returns every later frame's own trimap, and the
+            label maps <root>/<seq>/labels/<frame stem>.png (8-bit grey: 0 bg, 128 unknown, 255 fg, any other value
+            unlabelled) -- what run_video_matte(keyframes=...) takes
     V108  : <root>/VideoMatting108/{frame_corr.json, val_videos.txt, FG_done/<video>/<clip>/*.png (RGBA),
             BG_done2/...}; frame_corr maps an FG frame to its BG frame; a video's frames are the sorted keys of
             frame_corr whose dirname is the line of the set file
@@ -143,11 +146,26 @@ def resolve_bg(path):
     return path if os.path.exists(path) else os.path.splitext(path)[0] + ".png"
 
 
-def load_sequence(item, max_frames=None, decode_frames=True):
+LABEL_LEVELS = {0: 0, 128: 1, 255: 2}            # grey level of a labels/<stem>.png -> class (bg, unknown, fg); the rest: 255
+
+
+def read_label_map(path):
+    """labels/<stem>.png -> uint8 [H,W] with 0 bg, 1 unknown, 2 fg, 255 unlabelled (exact grey levels 0 / 128 / 255)."""
+    g = _imread(path, "L")
+    out = np.full(g.shape, 255, np.uint8)
+    for level, cls in LABEL_LEVELS.items():
+        out[g == level] = cls
+    return out
+
+
+def load_sequence(item, max_frames=None, decode_frames=True, keyframes=False):
     """Decode one item of either iterator into what run_video_matte takes.
 
     Returns dict(name, names=[file stems], frames=[uint8 BGR], and either trimap=one-hot [3,H,W] (demo) or
     alphas=[float32 [H,W] in 0..1], backgrounds=[uint8 BGR], gt_alpha_u8=[uint8 [H,W]] (V108)).
+    keyframes (demo layout): also keyframe_trimaps={frame index: one-hot [3,H,W]} of every frame that has a trimap file of
+    its own and label_maps={frame index: uint8 [H,W]} of every frame with a labels/<stem>.png; the first frame then needs no
+    trimap (``trimap`` is None without one) as long as some frame has.
     """
     from .video import trimap_file_to_onehot
     data_name, root, FG, BG, _a, TRI, seq_name = item
@@ -160,11 +178,26 @@ def load_sequence(item, max_frames=None, decode_frames=True):
         # the reference reads the trimap listed for each frame (dataset.py:879) and the model consumes the first
         # frame's: a clip whose FIRST frame has no trimap file cannot be evaluated (cv2.imread('') -> None there)
         tri = TRI[0] if TRI else ""
+        out["frame_paths"] = [os.path.join(root, p) for p in FG[:n]]
+        if keyframes:
+            # a frame's own trimap: the listed path carries the frame's stem (later frames repeat the most recent path)
+            own = {t: TRI[t] for t in range(n) if TRI[t] and os.path.splitext(os.path.basename(TRI[t]))[0] == names[t]}
+            if not own:
+                raise FileNotFoundError("sequence %s: no trimap for any of its %d frames (%s/%s/trimap/<frame>.png)"
+                                        % (seq_name, n, root, seq_name))
+            out["keyframe_trimaps"] = {t: trimap_file_to_onehot(read_trimap_unchanged(os.path.join(root, p)))
+                                       for t, p in own.items()}
+            out["trimap"] = out["keyframe_trimaps"].get(0)
+            out["label_maps"] = {}
+            for t in range(n):
+                lp = os.path.join(root, seq_name, "labels", names[t] + ".png")
+                if os.path.isfile(lp):
+                    out["label_maps"][t] = read_label_map(lp)
+            return out
         if not tri:
             raise FileNotFoundError("sequence %s: no trimap for its first frame (%s/%s/trimap/%s.png)"
                                     % (seq_name, root, seq_name, names[0] if names else "?"))
         out["trimap"] = trimap_file_to_onehot(read_trimap_unchanged(os.path.join(root, tri)))
-        out["frame_paths"] = [os.path.join(root, p) for p in FG[:n]]
         return out
     frames, gts = [], []
     for p in FG[:n]:

@@ -258,9 +258,23 @@ def pad_amounts(h, w, d):
     return lw, nw - w - lw, lh, nh - h - lh
 
 
-def bank_update(bank, new, first_frame, memorize, max_memory_num):
-    """Slot policy of reference models/alpha/model.py:472-493.  Returns (bank, released_slots)."""
+def _is_anchor(slot):
+    return isinstance(slot, dict) and bool(slot.get("anchor", False))
+
+
+def bank_update(bank, new, first_frame, memorize, max_memory_num, anchor=False):
+    """Slot policy of reference models/alpha/model.py:472-493, with ANCHOR slots (frames that were given a trimap: the first
+    frame's slot always, a keyframe's with ``anchor``; the flag lives in slot["anchor"] of the engine's dict slots, set here --
+    any other object is a plain slot).  For max_memory_num >= 2:
+    ``new`` is appended when it is an anchor, ``memorize`` is set, the bank has one slot or its last slot is an anchor --
+    otherwise it replaces the last slot; then, while the bank holds more than max_memory_num + (anchors - 1) slots, the
+    oldest slot that is not an anchor leaves.  Anchors stay until the next first_frame.  With one anchor (the first frame
+    alone) this is the reference's policy line for line: the cap is max_memory_num and the oldest non-anchor is index 1.
+    Returns (bank, released_slots)."""
     old = list(bank)
+    new_anchor = bool(anchor or first_frame)
+    if isinstance(new, dict):
+        new["anchor"] = new_anchor
     if max_memory_num == 0:
         nb = [new] if first_frame else bank
     elif max_memory_num == 1:
@@ -268,12 +282,15 @@ def bank_update(bank, new, first_frame, memorize, max_memory_num):
     else:
         if first_frame:
             nb = [new]
-        elif memorize or len(bank) == 1:
+        elif new_anchor or memorize or len(bank) == 1 or (bank and _is_anchor(bank[-1])):
             nb = bank + [new]
         else:
             nb = bank[:-1] + [new]
-        if len(nb) > max_memory_num:
-            nb = nb[:1] + nb[2:]
+        cap = max_memory_num + max(0, sum(1 for s in nb if _is_anchor(s)) - 1)
+        while len(nb) > cap:
+            # behind the head, which is the first frame's slot (always found: the cap is at least anchors + 1)
+            i = next(j for j in range(1, len(nb)) if not _is_anchor(nb[j]))
+            nb = nb[:i] + nb[i + 1:]
     released = [s for s in old + [new] if not any(s is k for k in nb)]
     return nb, released
 
@@ -695,7 +712,8 @@ class HipEngine:
             return self._frame_batch(*args, **kw)
 
     def _frame(self, a, fg, bg, tri_gt=None, first_frame=False, last_frame=False, memorize=False, max_memory_num=2,
-               dilate_kernel=None, frame_id=None, cls_override=None, frames_rgb=False, inputs_ready=None):
+               dilate_kernel=None, frame_id=None, cls_override=None, frames_rgb=False, inputs_ready=None, keyframe=False,
+               labels=None):
         """One call of EvalModel.forward (reference models/alpha/model.py:391-512) on the HIP path.
 
         a [1,1,1,H,W] in [0,1]; fg, bg [1,1,3,H,W] BGR 0..255; tri_gt [1,1,3,H,W] or None.
@@ -704,25 +722,48 @@ class HipEngine:
         inputs_ready: True = a / fg / bg are device tensors whose contents are complete (nothing still in flight writes
         them); a torch.cuda.Event = complete once that event has fired; None = unknown (ordered after everything issued on
         the launch stream so far).  Only matters for how early the query encoder may start.
+        keyframe / labels: re-anchoring a clip on a later frame (see _frame_batch).
         Returns the reference's 5-tuple (scaled_imgs, preds_trimap, tri_gt, preds_alpha, scaled_gts)."""
         return self._frame_batch([a], [fg], [bg], [tri_gt], first_frame, last_frame, memorize, max_memory_num, dilate_kernel,
-                                 frame_id, None if cls_override is None else [cls_override], frames_rgb, inputs_ready)[0]
+                                 frame_id, None if cls_override is None else [cls_override], frames_rgb, inputs_ready,
+                                 keyframe=keyframe, labels=labels)[0]
 
     def _frame_batch(self, a_l, fg_l, bg_l, tri_gt_l, first_frame=False, last_frame=False, memorize=False, max_memory_num=2,
                      dilate_kernel=None, frame_id=None, cls_override=None, frames_rgb=False, inputs_ready=None, train=None,
-                     _recheck=2):
+                     _recheck=2, keyframe=False, labels=None):
         """The same frame step for B independent sequences in LOCK-STEP (round 3): lists of B inputs of one resolution, one
         memory schedule (first_frame / last_frame / memorize / max_memory_num apply to all), per-sequence banks.  Every
         (train: buffers of the training-mode forward, otvm_amd/train.py -- the heads' full outputs and the raw logits are
         written there as well, and frame 0 memorises the ground-truth trimap.)  Every
         layer is ONE launch over the B images (otvm_conv_params.batch, otvm_gn_*_b, ...): the weights are read once, and
         the small maps of the encoders -- too few tiles for 256 CUs from one image -- fill the chip.  Each image is computed
-        exactly as a batch-1 call computes it (same tiles, same summation order).  Returns a list of B 5-tuples."""
+        exactly as a batch-1 call computes it (same tiles, same summation order).  Returns a list of B 5-tuples.
+        Two opt-in extensions of the reference's frame step, single sequence only (the reference consumes a trimap on the first
+        frame alone, alpha/model.py:425-443):
+          keyframe=True with a tri_gt on a later frame -- a FULL KEYFRAME: the padded trimap is the network's trimap input exactly
+            as on a first frame (otvm_pad_trimap), the STM segment is not run (no query encoder, no memory read: last_T_read
+            == 0), the bank is NOT reset, and the slot this frame memorises is an anchor (bank_update);
+          labels = uint8 [H,W] map (0 bg, 1 unknown, 2 fg, 255 unlabelled) on a later frame -- a CORRECTION: the steady route,
+            with otvm_trimap_apply_labels between the STM decoder's softmax and the encoding; with keyframe=True its slot is
+            an anchor as well."""
         dev, lib = self.dev, self.lib
         f32 = torch.float32
         B = len(a_l)
         if not (len(fg_l) == len(bg_l) == len(tri_gt_l) == B) or B < 1:
             raise ValueError("otvm_amd: a / fg / bg / tri_gt lists must have the same length")
+        keyframe = bool(keyframe)
+        if keyframe or labels is not None:
+            if B > 1 or train is not None:
+                raise NotImplementedError("otvm_amd: keyframe / labels apply to a single sequence (not to lock-step batches)")
+            if labels is not None and first_frame:
+                raise ValueError("otvm_amd: labels correct a propagated trimap; a first frame takes its trimap as tri_gt")
+            if keyframe and labels is None and tri_gt_l[0] is None:
+                raise ValueError("otvm_amd: keyframe=True needs the frame's trimap as tri_gt")
+            if max_memory_num < 2:
+                raise ValueError("otvm_amd: keyframe / labels need max_memory_num >= 2 (a bank of %d slot(s) holds no anchors)"
+                                 % max_memory_num)
+        kf_full = keyframe and labels is None and not first_frame   # a later frame that runs on its own trimap
+        no_segment = first_frame or kf_full
         main = torch.cuda.current_stream(dev)
         if isinstance(inputs_ready, torch.cuda.Event):
             main.wait_event(inputs_ready)                     # before anything below (a conversion, too) reads the inputs
@@ -766,6 +807,12 @@ class HipEngine:
             self._fgr_on = bool(self.foreground) and train is None
         elif bool(self.foreground) != self._fgr_on and train is None:
             raise RuntimeError("otvm_amd: `foreground` may only change at a clip's first frame")
+        lab = None
+        if labels is not None:
+            lab = labels if torch.is_tensor(labels) else torch.as_tensor(labels)
+            if lab.dtype != torch.uint8 or tuple(lab.shape) != (H, W):
+                raise ValueError("otvm_amd: labels must be a uint8 [%d,%d] map, got %s %s" % (H, W, lab.dtype, tuple(lab.shape)))
+            lab = lab.to(dev).contiguous()
         pl = self.plan(H, W, B)
         stream = self._stream()
         outs = [dict(scaled_imgs=torch.empty((1, 1, 3, H, W), dtype=f32, device=dev),
@@ -812,7 +859,7 @@ class HipEngine:
         # own), and -- when the caller vouches that the frame is already in device memory (inputs_ready) and the host runs
         # ahead of the device -- already under the previous frame's alpha network, which is still executing on the launch
         # stream.  Its buffers (SQ, the q_ trunk, QK, M4[512:]) were last read by the previous frame's STM decoder (ev_dec).
-        use_side = self.prof is None and self.use_side_stream and not first_frame
+        use_side = self.prof is None and self.use_side_stream and not no_segment
         ev_q = ev_s2 = None
         split = None                                          # memory read started on a side stream (see below)
         if use_side:
@@ -867,7 +914,8 @@ class HipEngine:
                     self._preprocess_rest(pl, pps[b], par, outs[b]["scaled_imgs"], False, side2.cuda_stream, b)
             if self.precision == L.PREC_F16X3:
                 if pend is not None:
-                    nb, _ = bank_update(self.bank, pend["slot"], pend["first_frame"], pend["memorize"], pend["max_memory_num"])
+                    nb, _ = bank_update(self.bank, pend["slot"], pend["first_frame"], pend["memorize"], pend["max_memory_num"],
+                                        pend["anchor"])
                     old = [s_ for s_ in nb if s_ is not pend["slot"]]
                     fresh = [pend["slot"]] if any(s_ is pend["slot"] for s_ in nb) else []
                 else:
@@ -902,7 +950,7 @@ class HipEngine:
             tri_srcs.append(tri_src)
 
         self.last_T_read = 0
-        if first_frame:
+        if no_segment:
             for b in range(B):
                 L.check(lib.otvm_pad_trimap(tri_srcs[b].data_ptr(), H, W, pl.PROBS_B[b].data_ptr(), pl.Hp, pl.Wp, pl.lh, pl.lw,
                                             stream), "pad_trimap")
@@ -938,6 +986,9 @@ class HipEngine:
                 self.prof.append(("memory_read", 1280.0 * len(self.bank) * pl.hw * pl.hw * B, e0, e1, len(self.bank)))
             pl.run("segment_b", stream)
             self.guard(pl.L4, "propagated trimap logits", stream, frame_id)
+            if lab is not None:
+                L.check(lib.otvm_trimap_apply_labels(pl.PROBS_B[0].data_ptr(), lab.data_ptr(), H, W, pl.Hp, pl.Wp, pl.lh, pl.lw,
+                                                     stream), "trimap_apply_labels")
             if train is not None and train.get("seg_logits") is not None:
                 for b in range(B):                             # the cross-entropy takes the logits (model.py:286-288)
                     l4 = pl.L4.img(b)
@@ -947,7 +998,7 @@ class HipEngine:
                 self.ev_dec = torch.cuda.Event()              # the query encoder's buffers are free again
                 self.ev_dec.record(main)
         pl.encode(stream, cls_override)
-        if not first_frame and EVDEC_LATE:
+        if not no_segment and EVDEC_LATE:
             # round 4: the NEXT frame's query encoder (side stream) is released behind the trimap encoding, not in front of
             # it: its fused-bottleneck kernels (one workgroup per CU, every register of the CU) otherwise take the chip from
             # the three small kernels of the encoding -- on the frame's serial chain -- which then wait for whole workgroups
@@ -979,7 +1030,7 @@ class HipEngine:
             slot = pl.new_slot()
             slot["frame"] = frame_id
             self.pending = dict(plan=pl, par=par, slot=slot, first_frame=first_frame, memorize=memorize,
-                                max_memory_num=max_memory_num)
+                                max_memory_num=max_memory_num, anchor=first_frame or keyframe)
         for b in range(B):
             o = outs[b]
             L.check(lib.otvm_crop_outputs(pl.ALPHA_P_B[b].data_ptr(), pl.TRI_P_B[b].data_ptr(), pl.Hp, pl.Wp, H, W, pl.lh, pl.lw,
@@ -1008,13 +1059,15 @@ class HipEngine:
                 if verdict == "off":
                     self._drop_plans()                        # (rebuilt below without the predicted tails)
                 return self._frame_batch(a_l, fg_l, bg_l, tri_gt_l, first_frame, last_frame, memorize, max_memory_num, dilate_kernel,
-                                         frame_id, cls_override, frames_rgb, None, train, _recheck=_recheck - 1)
+                                         frame_id, cls_override, frames_rgb, None, train, _recheck=_recheck - 1, keyframe=keyframe,
+                                         labels=labels)
         elif self.gn_predict_off and pl._predicted and first_frame:
             # the guard tripped in the middle of the previous clip: this clip's first frame ran on a plan that still predicts --
             # rebuild now and compute it again
             self._drop_plans()
             return self._frame_batch(a_l, fg_l, bg_l, tri_gt_l, first_frame, last_frame, memorize, max_memory_num, dilate_kernel,
-                                     frame_id, cls_override, frames_rgb, None, train, _recheck=0)
+                                     frame_id, cls_override, frames_rgb, None, train, _recheck=0, keyframe=keyframe,
+                                     labels=labels)
         if self.check_finite and not all(bool(torch.isfinite(o["alpha"]).all()) for o in outs):
             raise FloatingPointError("otvm_amd: non-finite alpha at frame %d -- an activation probably left fp16's range on the "
                                      "f16x3 path; rerun with model.precision = 'f32' (exact-fp32 MFMA)" % frame_id)
@@ -1084,16 +1137,37 @@ class HipEngine:
         pl.run("mem_stem%d" % pend["par"], stream, tstream)
         pl.run("mem_trunk", stream, tstream)
         pl.kv_into_slot(slot, stream)
-        self.bank, released = bank_update(self.bank, slot, pend["first_frame"], pend["memorize"], pend["max_memory_num"])
+        self.bank, released = bank_update(self.bank, slot, pend["first_frame"], pend["memorize"], pend["max_memory_num"],
+                                          pend["anchor"])
         self.free_slots.extend(released)
 
-    def bank_frames(self):
-        """Frame ids resident in the bank, including a memorize that is still deferred (host-side policy only)."""
+    def _bank_with_pending(self):
         bank = list(self.bank)
         pend = self.pending
         if pend is not None:
-            bank, _ = bank_update(bank, pend["slot"], pend["first_frame"], pend["memorize"], pend["max_memory_num"])
-        return [s["frame"] for s in bank]
+            bank, _ = bank_update(bank, pend["slot"], pend["first_frame"], pend["memorize"], pend["max_memory_num"],
+                                  pend["anchor"])
+        return bank
+
+    def bank_frames(self):
+        """Frame ids resident in the bank, including a memorize that is still deferred (host-side policy only)."""
+        return [s["frame"] for s in self._bank_with_pending()]
+
+    def bank_anchors(self):
+        """Frame ids of the resident ANCHOR slots (frames that were given a trimap), a deferred memorize included."""
+        return [s["frame"] for s in self._bank_with_pending() if _is_anchor(s)]
+
+    def drop_non_anchors(self):
+        """Leave only the anchor slots in the bank (a sweep in the other direction starts from the keyframes alone).  A deferred
+        memorize of an anchor is carried out first; one of any other frame is dropped with its slot, unmemorised."""
+        pend = self.pending
+        if pend is not None and (pend["anchor"] or pend["first_frame"]):
+            self.flush()
+        elif pend is not None:
+            self.pending = None
+            self.free_slots.append(pend["slot"])
+        self.free_slots.extend(s for s in self.bank if not _is_anchor(s))
+        self.bank = [s for s in self.bank if _is_anchor(s)]
 
     def flush(self):
         """Run a deferred memorize now (bank introspection, end of stream)."""

@@ -13,6 +13,10 @@ accumulated on the device and reduced over ranks (--all-metrics: also Grad, Conn
 writes that foreground over a new background (an image, resized once on the host to the clip's resolution, or a colour),
 <out>/comp/<seq>/<name>.png.  Both work for the demo and the VideoMatting108 layouts and with --gpus N; with --batch > 1 they
 are refused (as --viz is).
+--keyframes (demo layout): every trimap/<stem>.png of a clip -- not only the first frame's -- is a full keyframe and every
+labels/<stem>.png (8-bit grey: 0 bg, 128 unknown, 255 fg, anything else unlabelled) a correction of the propagated trimap; the
+clip is matted from the earliest trimap forward and then backward (video.keyframe_schedule), so its first frame needs no trimap.
+Without the flag those files are ignored.  Frames are decoded up front in this mode; refused with --batch > 1.
 Frame IO runs through otvm_amd/io_pipeline.py: the demo flow decodes ahead in a thread pool and uploads on a copy
 stream, both flows download the 8-bit alphas asynchronously and PNG-encode them in a pool (the reference's loop blocks
 on .cpu() + cv2.imwrite per frame, eval.py:209-217).
@@ -54,6 +58,8 @@ def main(argv=None):
     ap.add_argument("--fgr", action="store_true", help="also write the foreground estimate as RGBA PNGs (<out>/fgr/<seq>/)")
     ap.add_argument("--composite", default=None, metavar="PATH|R,G,B",
                     help="also write the foreground composited over a new background image or colour (<out>/comp/<seq>/)")
+    ap.add_argument("--keyframes", action="store_true",
+                    help="demo layout: use every trimap/<stem>.png as a full keyframe and every labels/<stem>.png as a correction")
     ap.add_argument("--max-frames", type=int, default=None, help="only the first N frames of every sequence")
     ap.add_argument("--weights", default=None)
     ap.add_argument("--synthetic-weights", action="store_true")
@@ -139,7 +145,8 @@ def main(argv=None):
         args.batch = 1
         # (--viz and --sync-io are single-clip features -- matte_batch writes no viz frames and decodes every clip of a group up
         #  front -- so they keep batch 1 unless --batch is given explicitly)
-        if world > 1 and any(k is not None for k in keys) and not (args.viz or args.sync_io or args.fgr or args.composite):
+        if world > 1 and any(k is not None for k in keys) and not (args.viz or args.sync_io or args.fgr or args.composite
+                                                                   or args.keyframes):
             def padded(k):
                 lw, uw, lh, uh = pad_amounts(k[0], k[1], 32)
                 return (k[0] + lh + uh) * (k[1] + lw + uw)
@@ -150,6 +157,11 @@ def main(argv=None):
     if args.batch > 1 and (args.fgr or args.composite):
         raise SystemExit("eval_cli: --batch %d steps clips in lock-step through matte_batch, which implements neither --fgr nor "
                          "--composite; drop one of them" % args.batch)
+    if args.keyframes and not args.demo:
+        raise SystemExit("eval_cli: --keyframes reads the demo layout's trimap/ and labels/ folders; add --demo")
+    if args.keyframes and args.batch > 1:
+        raise SystemExit("eval_cli: --batch %d steps clips in lock-step through matte_batch, which does not implement --keyframes"
+                         % args.batch)
     if rank == 0:
         print("eval_cli: %d rank(s), lock-step batch %d per rank" % (world, args.batch))
     if distributed:
@@ -169,7 +181,9 @@ def main(argv=None):
 
     def matte(seq):
         demo = seq["item"][0] == "demo"
-        data = datasets.load_sequence(seq["item"], max_frames=args.max_frames, decode_frames=not demo or args.sync_io)
+        keyed = demo and args.keyframes                     # frames in schedule order: decoded up front, not prefetched
+        data = datasets.load_sequence(seq["item"], max_frames=args.max_frames, decode_frames=not demo or args.sync_io or keyed,
+                                      keyframes=keyed)
         outdir = os.path.join(root_out, "pred", seq["name"])
         os.makedirs(outdir, exist_ok=True)
         vizdir = os.path.join(args.out, "viz", "test", helpers.get_model_name(cfg), "viz", seq["name"])
@@ -182,7 +196,7 @@ def main(argv=None):
         fwriter = AlphaWriter(dev, os.path.join(args.out, "fgr", seq["name"]), png_names) if args.fgr else None
         cwriter = AlphaWriter(dev, os.path.join(args.out, "comp", seq["name"]), png_names) if args.composite is not None else None
         eng_of = model.module
-        bgr = not (demo and not args.sync_io)              # the prefetcher hands out RGB frames, the decoded arrays are BGR
+        bgr = not (demo and not args.sync_io and not keyed)   # the prefetcher hands out RGB frames, the decoded arrays are BGR
 
         def new_background():
             if args.composite is None:
@@ -208,14 +222,18 @@ def main(argv=None):
             if args.viz:
                 viz.write_viz_frame(os.path.join(vizdir, "f%d.jpg" % i), out)
         if demo:
-            if args.sync_io:
+            if args.sync_io or keyed:
                 frames, rgb, pre = data["frames"], False, None
             else:                                  # decode ahead + pinned upload on a copy stream (RGB order)
                 pre = FramePrefetcher(data["frame_paths"], dev)
                 frames, rgb = _Listish(pre), True
-            res = run_video_matte(model, frames, trimap=data["trimap"], skip=args.skip, max_num=args.max_num,
+            kf = {**data["keyframe_trimaps"], **data["label_maps"]} if keyed else None
+            both = keyed and sorted(set(data["keyframe_trimaps"]) & set(data["label_maps"]))
+            if both:
+                raise SystemExit("eval_cli: sequence %s has a trimap AND a label map for frame(s) %s" % (seq["name"], both))
+            res = run_video_matte(model, frames, trimap=None if keyed else data["trimap"], skip=args.skip, max_num=args.max_num,
                                   on_frame=save, device=dev, frames_are_rgb=rgb, keep_on_device=True,
-                                  foreground=want_fgr, new_background=new_background())
+                                  foreground=want_fgr, new_background=new_background(), keyframes=kf)
             if pre is not None:
                 pre.close()
         else:

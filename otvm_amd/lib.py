@@ -129,6 +129,7 @@ _PROTOS = {
     "otvm_preprocess": (i32, [C.POINTER(PreprocessParams), vp]),
     "otvm_pad_trimap": (i32, [vp, i32, i32, vp, i32, i32, i32, i32, vp]),
     "otvm_upsample4_softmax3": (i32, [vp, i32, i32, i32, vp, vp]),
+    "otvm_trimap_apply_labels": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "otvm_trimap_encode_ws_bytes": (i64, [i32, i32]),
     "otvm_trimap_encode": (i32, [vp, i32, i32, vp, vp, vp, i32, vp, i32, vp, vp]),
     "otvm_fba_head": (i32, [vp, i32, vp, vp, i32, vp, i32, i64, vp, i32, vp, vp, i32, vp]),

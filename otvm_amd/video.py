@@ -19,6 +19,50 @@ def memory_schedule(i_seq, height, width, skip=10, max_num=5):
     return memorize, max_num, large
 
 
+def _keyframe_kind(v):
+    """"key" (a full trimap: one-hot [3,H,W]) or "labels" (a uint8 [H,W] label map) of one entry of ``keyframes``."""
+    if isinstance(v, str):
+        if v not in ("key", "labels"):
+            raise ValueError("keyframes: an entry is a one-hot trimap [3,H,W], a uint8 label map [H,W], 'key' or 'labels'; got %r" % v)
+        return v
+    nd = v.dim() if torch.is_tensor(v) else np.asarray(v).ndim
+    if nd not in (2, 3):
+        raise ValueError("keyframes: an entry is a one-hot trimap [3,H,W] or a uint8 label map [H,W], got %d dimensions" % nd)
+    return "key" if nd == 3 else "labels"
+
+
+def keyframe_schedule(T, keyframes, skip=10):
+    """Order in which a clip of ``T`` frames with trimaps / label maps on several frames is matted (pure host function).
+
+    keyframes: {frame: one-hot trimap [3,H,W] (a FULL keyframe) | uint8 label map [H,W] (a correction)}; the strings "key" /
+    "labels" stand for the arrays.  Returns the steps (t, kind, first_frame, last_frame, memorize), kind in "key" / "labels" /
+    "frame".  With k0 the earliest full keyframe (there must be one):
+      A. every full keyframe in ascending order, k0 as the clip's first_frame, the others as keyframe steps: all of them are in
+         the memory bank -- as anchors -- before any other frame is matted;
+      B. forward over k0+1 .. T-1 without the full keyframes (their outputs exist), memorize = (t - k0) % skip == 0;
+      C. backward over k0-1 .. 0 (the driver first drops every slot that is not an anchor), memorize = (k0 - t) % skip == 0.
+    Only the last step issued carries last_frame.  A label map is applied at its frame in either sweep.  ``skip`` is the
+    effective one (memory_schedule's large-input rule applied by the caller); skip <= 2 never memorises (eval.py:186-189).
+    keyframes = {0: trimap} gives eval.py:178-189 exactly."""
+    kinds = {int(t): _keyframe_kind(v) for t, v in keyframes.items()}
+    for t in kinds:
+        if not 0 <= t < T:
+            raise ValueError("keyframes: frame %d lies outside the clip (%d frames)" % (t, T))
+    keys = sorted(t for t, k in kinds.items() if k == "key")
+    if not keys:
+        raise ValueError("keyframes: at least one full keyframe (a one-hot trimap [3,H,W]) is required")
+    k0 = keys[0]
+
+    def mem(d):
+        return (d % skip) == 0 if skip > 2 else False
+    steps = [(k, "key", k == k0, False, mem(k - k0)) for k in keys]
+    steps += [(t, kinds.get(t, "frame"), False, False, mem(t - k0)) for t in range(k0 + 1, T) if kinds.get(t) != "key"]
+    steps += [(t, kinds.get(t, "frame"), False, False, mem(k0 - t)) for t in range(k0 - 1, -1, -1)]
+    t, kind, first, _, m = steps[-1]
+    steps[-1] = (t, kind, first, True, m)
+    return steps
+
+
 def trimap_file_to_onehot(tri):
     """Grayscale / 3-channel trimap image -> one-hot float32 [3,H,W] (bg, unknown, fg): dataset.py:880-893."""
     tri = np.asarray(tri)
@@ -82,7 +126,7 @@ def _foreground_option(core, on):
 def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, skip=10, max_num=5,
                     frames_are_rgb=False, on_frame=None, device=None, keep_on_device=False, gt_alpha_u8=None,
                     gt_mask_u8=None, gt_mask=None, gt_image_metrics=False, gt_flow_metrics=False, foreground=False,
-                    new_background=None):
+                    new_background=None, keyframes=None):
     """Matte one sequence.
 
     model       : EvalModel (optionally wrapped in nn.DataParallel), on the GPU
@@ -102,27 +146,58 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
     new_background : composite that foreground over a new background -> "comp_u8" [T,H,W,3].  A tuple (c0, c1, c2) is a
                   colour, a uint8 [H,W,3] array / tensor an image of the frames' resolution, a list one of those per frame;
                   all in the frames' channel order (switches ``foreground`` on: the composite needs F)
+    keyframes   : {frame: one-hot trimap [3,H,W] | uint8 label map [H,W] (0 bg, 1 unknown, 2 fg, 255 unlabelled)}, together
+                  with or instead of ``trimap`` (= {0: trimap}).  A trimap makes its frame a FULL keyframe (matted from that
+                  trimap, memorised as an anchor slot the bank never evicts), a label map a correction of the propagated trimap.
+                  The clip is matted in the order of keyframe_schedule -- the keyframes, then forward from the earliest one,
+                  then backward from it to frame 0 -- so ``frames`` must allow random access; on_frame fires in that order
+                  with the frame's index.  Everything returned (and the metrics) is in natural frame order.
     Returns dict(alpha=[T,H,W] float32, alpha_u8=[T,H,W] uint8 (truncated, eval.py:209), trimap=[T,3,H,W],
-    bank_frames=[per frame: ids of the frames resident in the memory bank after that frame's update]).
+    bank_frames=[per frame: ids of the frames resident in the memory bank after that frame's update]) and, when ``keyframes``
+    was given, anchor_frames=[per frame: those of them that are anchors], schedule=[the steps issued, keyframe_schedule's tuples].
     """
     frames = list(frames) if not (hasattr(frames, "shape") or hasattr(frames, "__getitem__")) else frames
     T = len(frames)
     dev = device or next(model.parameters()).device
-    out_a, out_u8, out_t, bank_log = [], [], [], []
-    out_f, out_c, bg_cache = [], [], {}
+    out_a, out_u8, out_t, bank_log, anchor_log = [None] * T, [None] * T, [None] * T, [None] * T, [None] * T
+    out_f, out_c, bg_cache = [None] * T, [None] * T, {}
     core = model.module if hasattr(model, "module") else model
     foreground = bool(foreground) or new_background is not None
     metrics = (ClipMetrics(dev, image_metrics=gt_image_metrics, flow_metrics=gt_flow_metrics) if gt_alpha_u8 is not None
                else None)
     # loop invariants: the user trimap (25 MB as fp32 at 1080p) is uploaded once, not once per frame; the dummy alpha
     # of the trimap flow is one tensor for the whole clip
-    tri_dev = None
-    if trimap is not None:
-        t = _as_tensor(trimap)
-        tri_dev = t.to(dev).float()[None, None]
+    keyed = keyframes is not None                     # the caller asked for keyframes: the result carries the extra keys
+    if keyframes is not None:
+        if alphas is not None:
+            raise ValueError("run_video_matte: keyframes belong to the trimap flow (no per-frame alphas)")
+        keyframes = {int(t): v for t, v in keyframes.items()}
+        if trimap is not None:
+            if 0 in keyframes:
+                raise ValueError("run_video_matte: frame 0 has both `trimap` and an entry of `keyframes`")
+            keyframes[0] = trimap
+    elif trimap is not None:
+        keyframes = {0: trimap}
+    tri_devs, lab_devs, steps, k0 = {}, {}, None, 0
+    if keyframes is not None and T > 0:
+        for t, v in keyframes.items():
+            if _keyframe_kind(v) == "key":
+                tri_devs[t] = _as_tensor(v).to(dev).float()[None, None]
+            else:
+                lab_devs[t] = _as_tensor(v).to(dev)
+        if not tri_devs:
+            raise ValueError("run_video_matte: keyframes need at least one full trimap (one-hot [3,H,W])")
+        k0 = min(tri_devs)
+        # the schedule takes the effective skip: the large-input rule needs the resolution, which the trimaps carry
+        large = memory_schedule(0, tri_devs[k0].shape[-2], tri_devs[k0].shape[-1], skip, max_num)[2]
+        steps = keyframe_schedule(T, {t: "key" for t in tri_devs} | {t: "labels" for t in lab_devs},
+                                  int(skip * 2) if large else skip)
+    elif T > 0:
+        steps = [(i, "frame", i == 0, i == T - 1, None) for i in range(T)]          # alpha flow: eval.py's loop as it is
+    natural = steps is None or all(st[0] == j for j, st in enumerate(steps))
     ones = None
     with _foreground_option(core, foreground):
-        for i in range(T):
+        for i, kind, first_frame, last_frame, step_memorize in (steps or []):
             f = _as_tensor(frames[i])
             b = _as_tensor(backgrounds[i]) if backgrounds is not None else None
             extra = {}
@@ -142,7 +217,7 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                     # (no copy made here), no separately uploaded background, and the trimap flow's constant alpha -- a per-frame
                     # alpha is written by the launch stream just below.  Otherwise the launch stream waits for the upload
                     # and the model orders its side streams behind the launch stream.
-                    if b is None and fg is f and trimap is not None:
+                    if b is None and fg is f and keyframes is not None:
                         extra["_inputs_ready"] = ready
                     else:
                         torch.cuda.current_stream(dev).wait_event(ready)
@@ -159,43 +234,53 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                     bg = b.permute(2, 0, 1)[None, None].contiguous()
                 else:
                     bg = fg
-            if trimap is not None:
+            if keyframes is not None:
                 if ones is None or ones.shape[-2:] != (H, W):
                     ones = torch.ones(1, 1, 1, H, W, device=dev)
-                a, tri_gt = ones, tri_dev
+                # (as eval.py does, every frame is handed a trimap -- it comes back as out[2]; only a keyframe consumes it)
+                a, tri_gt = ones, tri_devs.get(i, tri_devs[k0])
+                if kind == "key" and not first_frame:
+                    extra["keyframe"] = True
+                elif kind == "labels":
+                    extra["labels"] = lab_devs[i]
+                if i == k0 - 1:
+                    core.drop_non_anchors()                       # the backward sweep starts from the keyframes alone
             else:
                 al = alphas[i]
                 al = _as_tensor(al)
                 a = al.to(dev).float()[None, None, None]
                 tri_gt = None
             memorize, max_memory_num, large = memory_schedule(i, H, W, skip, max_num)
+            if step_memorize is not None:
+                memorize = step_memorize
             if foreground:
                 core.set_background(None if new_background is None else _background_at(new_background, i, dev, bg_cache))
-            out = model(a, fg, bg, tri=None, tri_gt=tri_gt, first_frame=(i == 0), last_frame=(i == T - 1),
-                        memorize=memorize, max_memory_num=max_memory_num, large_input=large, **extra)
+            out = model(a, fg, bg, tri=None, tri_gt=tri_gt, first_frame=first_frame, last_frame=last_frame,
+                        memorize=memorize, max_memory_num=max_memory_num, large_input=large, _frame_id=i, **extra)
             alpha = out[3][0, 0, 0]
             u8 = core._engine.last_alpha_u8
-            bank_log.append(list(core.memories["frames"]))          # frame ids resident after this frame's update (host list)
-            if metrics is not None:
-                g = gt_alpha_u8[i]
-                g = _as_tensor(g)
-                mk = gt_mask
-                if gt_mask_u8 is not None:
-                    mk = gt_mask_u8[i]
-                    mk = (_as_tensor(mk)).to(dev)
-                metrics.add(u8, g.to(dev), mk)
+            mem_now = core.memories                                 # frame ids resident after this frame's update (host lists)
+            bank_log[i], anchor_log[i] = list(mem_now["frames"]), list(mem_now["anchors"])
+            if metrics is not None and natural:
+                _metrics_add(metrics, u8, i, gt_alpha_u8, gt_mask_u8, gt_mask, dev)
             if on_frame is not None:
                 on_frame(i, alpha, u8, out)
             if keep_on_device:
-                out_a.append(alpha), out_u8.append(u8), out_t.append(out[1][0, 0])
+                out_a[i], out_u8[i], out_t[i] = alpha, u8, out[1][0, 0]
             else:
-                out_a.append(alpha.cpu()), out_u8.append(u8.cpu()), out_t.append(out[1][0, 0].cpu())
+                out_a[i], out_u8[i], out_t[i] = alpha.cpu(), u8.cpu(), out[1][0, 0].cpu()
             if foreground:
                 eng = core._engine
-                out_f.append(eng.last_rgba_u8 if keep_on_device else eng.last_rgba_u8.cpu())
+                out_f[i] = eng.last_rgba_u8 if keep_on_device else eng.last_rgba_u8.cpu()
                 if new_background is not None:
-                    out_c.append(eng.last_comp_u8 if keep_on_device else eng.last_comp_u8.cpu())
+                    out_c[i] = eng.last_comp_u8 if keep_on_device else eng.last_comp_u8.cpu()
+    if metrics is not None and not natural:
+        # the pair terms (dtSSD, MESSDdt) depend on the order: fed in natural frame order from the kept 8-bit alphas
+        for i in range(T):
+            _metrics_add(metrics, out_u8[i].to(dev), i, gt_alpha_u8, gt_mask_u8, gt_mask, dev)
     res = dict(alpha=torch.stack(out_a), alpha_u8=torch.stack(out_u8), trimap=torch.stack(out_t), bank_frames=bank_log)
+    if keyed:
+        res.update(anchor_frames=anchor_log, schedule=list(steps or []))
     if foreground:
         res["fgr_u8"] = torch.stack(out_f)
         if new_background is not None:
@@ -205,9 +290,17 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
     return res
 
 
+def _metrics_add(metrics, u8, i, gt_alpha_u8, gt_mask_u8, gt_mask, dev):
+    g = _as_tensor(gt_alpha_u8[i])
+    mk = gt_mask
+    if gt_mask_u8 is not None:
+        mk = _as_tensor(gt_mask_u8[i]).to(dev)
+    metrics.add(u8, g.to(dev), mk)
+
+
 def run_video_matte_batch(model, clips, trimaps=None, alphas=None, backgrounds=None, skip=10, max_num=5, frames_are_rgb=False,
                           device=None, keep_on_device=False, on_frame=None, gt_alpha_u8=None, gt_mask=None,
-                          gt_image_metrics=False, gt_flow_metrics=False, foreground=False, new_background=None):
+                          gt_image_metrics=False, gt_flow_metrics=False, foreground=False, new_background=None, keyframes=None):
     """Matte B sequences of one resolution in LOCK-STEP (round 3): frame i of every clip goes through the network in one
     batched step (EvalModel.forward_batch: one launch per layer over the B images, per-sequence memory banks).
     clips: list of B frame arrays ([T_b,H,W,3] uint8 / float, BGR unless frames_are_rgb); trimaps: list of B first-frame
@@ -225,6 +318,8 @@ def run_video_matte_batch(model, clips, trimaps=None, alphas=None, backgrounds=N
     foreground / new_background: as run_video_matte ("fgr_u8" [T_b,H,W,4], "comp_u8" [T_b,H,W,3] per clip); new_background = a
     list of B entries, one per clip, each what run_video_matte takes (colour tuple, image, or per-frame list).
     Returns a list of B dicts (alpha, alpha_u8, trimap, bank_frames[, metrics][, fgr_u8][, comp_u8])."""
+    if keyframes is not None:
+        raise NotImplementedError("run_video_matte_batch: keyframes are a single-clip feature (run_video_matte)")
     B = len(clips)
     lens = [len(c) for c in clips]
     T = max(lens)
