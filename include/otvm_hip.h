@@ -65,7 +65,9 @@ const char* otvm_last_error(void);
                                  (21, additive: the foreground outputs -- the entry points with _fgr in their names and the output
                                   kernel of otvm_fgr_params are NEW symbols only; no existing struct, prototype or result changed, so a
                                   caller built against the earlier 21 runs unchanged and the number stays;
-                                  likewise otvm_trimap_apply_labels, the label pass of the keyframe corrections) */
+                                  likewise otvm_trimap_apply_labels, the label pass of the keyframe corrections;
+                                  likewise working-resolution matting: otvm_downsample_u8 / _trimap / _labels, otvm_guided_ws_bytes,
+                                  otvm_guided_coeffs and otvm_guided_apply with their struct otvm_guided_params) */
 int otvm_abi_version(void);
 
 /* ---------------------------------------------------------------- weights (load time) ----------
@@ -482,6 +484,60 @@ typedef struct otvm_fgr_params {
     int u8_rgb;
 } otvm_fgr_params;
 int otvm_fgr_outputs(const otvm_fgr_params* p, void* stream);
+
+/* ---------------------------------------------------------------- working-resolution matting ----
+ * The network runs on a reduced copy of the frame (integer scale s = 2, 3, 4; working size h = ceil(H / s), w = ceil(W / s)) and
+ * its outputs return to the frame's resolution through the colour-guide fast guided filter (He & Sun).  Everything below is
+ * restated operation by operation in tests/guided_ref.py; the kernels use no atomics, so two calls give equal bits.
+ *
+ * Reductions (integer arithmetic):
+ *   otvm_downsample_u8     uint8 [H,W,3] -> [h,w,3]: mean of the s x s block, clipped at the bottom / right edge to its n
+ *                          source pixels: byte = (sum + n / 2) / n
+ *   otvm_downsample_trimap planar one-hot float [3,H,W] (bg, unknown, fg) -> [3,h,w], conservative: fg only if plane 2 is 1.f
+ *                          on every pixel of the block, bg only if plane 0 is; otherwise unknown (a block for which both hold
+ *                          is not one-hot input: unknown).  The unknown band never shrinks
+ *   otvm_downsample_labels uint8 [H,W] (0 bg, 1 unknown, 2 fg, else unlabelled) -> [h,w]: 255 if any pixel of the block is not
+ *                          a class, the common class if all agree, otherwise 1 (unknown)                                    */
+int otvm_downsample_u8(const uint8_t* src, int H, int W, int s, uint8_t* dst, void* stream);
+int otvm_downsample_trimap(const float* src, int H, int W, int s, float* dst, void* stream);
+int otvm_downsample_labels(const uint8_t* src, int H, int W, int s, uint8_t* dst, void* stream);
+
+/* Guided filter.  otvm_guided_coeffs (working resolution): window (2r+1)^2, r = 1..4, clipped at the borders to its N pixels.
+ * Each target is quantised once, P = (int)(min(max(p, 0), 1) * 65535.f + 0.5f), so the window sums of I_c, I_c I_d, P and
+ * I_c P are exact 32-bit integers.  Per pixel in fp64, one IEEE operation per step:
+ *   s_cd = (N sum(I_c I_d) - sum(I_c) sum(I_d)) / (N N 65025) [+ eps on the diagonal]
+ *   p_c  = (N sum(I_c P) - sum(I_c) sum(P)) / (N N 255 65535)
+ *   adjugate of the symmetric s: c00 = s11 s22 - s12 s12, c01 = s02 s12 - s01 s22, c02 = s01 s12 - s02 s11,
+ *                                c11 = s00 s22 - s02 s02, c12 = s01 s02 - s00 s12, c22 = s00 s11 - s01 s01
+ *   det = (s00 c00 + s01 c01) + s02 c02;  a_i = ((c_i0 p_0 + c_i1 p_1) + c_i2 p_2) / det
+ *   b = (sum(P) / N) / 65535 - ((a_0 m_0 + a_1 m_1) + a_2 m_2),  m_c = (sum(I_c) / N) / 255
+ * (a constant target gives a = 0 and b = P / 65535 exactly).  (a_0, a_1, a_2, b) is rounded to fp32 into ws [h,w,C,4]; coef
+ * [h,w,C,4] receives its box mean over the same clipped window: fp64 sums of rows in ascending x, then of columns in ascending y,
+ * divided by N, rounded to fp32.  ws: otvm_guided_ws_bytes(h, w, C) bytes, 16-byte aligned, no initialisation (it holds the
+ * un-averaged coefficients afterwards); one ws serves one stream at a time.
+ * otvm_guided_apply (full resolution, fp32, one IEEE operation per step): per pixel (X, Y) the mean coefficients are looked up
+ * bilinearly with half-pixel centres -- t = 2X + 1 - s, x0 = floor(t / 2s), fx = (float)(t - 2s x0) / (float)(2s), x0 and x0 + 1
+ * clamped to [0, w-1], rows alike; v = top + fy * (bot - top) with top = c00 + fx * (c01 - c00), bot = c10 + fx * (c11 - c10) --
+ * then q = ((a_0 I_0 + a_1 I_1) + a_2 I_2) + b with I = (float)byte * (1.f / 255.f), clamped: q < 0 ? 0 : (q > 1 ? 1 : q); a NaN q
+ * (non-finite coefficients: an eps too small for a constant guide region) gives 0 by an explicit select.
+ * Target 0 goes to alpha [H,W] and alpha_u8 [H,W] = (uint8)(alpha * 255.f) (truncation, as otvm_crop_outputs; may be NULL),
+ * targets 1..3 (C = 4: the F planes) to fgr [3,H,W].  RGBA / composite bytes: otvm_fgr_outputs on these with Hp = H, Wp = W,
+ * lh = lw = 0.  The guide's three bytes are used in the order they are stored, in both calls.                            */
+typedef struct otvm_guided_params {
+    int H, W, s, h, w;            /* full size, scale (2, 3, 4), working size (ceil(H / s), ceil(W / s))                  */
+    int r, C;                     /* window radius 1..4; targets: 1 (alpha) or 4 (alpha + F)                              */
+    double eps;                   /* regulariser on the [0,1] scale, > 0                                                  */
+    const uint8_t* guide_full;    /* uint8 [H,W,3]: the frame (apply)                                                     */
+    const uint8_t* guide_work;    /* uint8 [h,w,3]: the working frame the network saw (coeffs)                            */
+    const float* target[4];       /* C planes [h,w] fp32 (coeffs)                                                         */
+    float* coef;                  /* [h,w,C,4] fp32, 16-byte aligned: written by coeffs, read by apply                    */
+    float* alpha;                 /* outputs of apply                                                                     */
+    uint8_t* alpha_u8;
+    float* fgr;
+} otvm_guided_params;
+int64_t otvm_guided_ws_bytes(int h, int w, int C);      /* -1 for an empty image or C not in {1, 4} */
+int otvm_guided_coeffs(const otvm_guided_params* p, void* ws, void* stream);
+int otvm_guided_apply(const otvm_guided_params* p, void* stream);
 
 /* first-frame trimap from a GT alpha (alpha/model.py:342-362): unknown = dilate(0<a<1) with a
  * (2r+1)^2 max filter, fg = (a==1), bg = (a==0); out planar one-hot [3,H,W]; ws >= H*W bytes      */

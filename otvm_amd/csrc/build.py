@@ -29,6 +29,7 @@ SOURCES = [
     ("resample.hip", ["-ffp-contract=off"]),
     ("glue.hip", ["-ffp-contract=off"]),
     ("fgr.hip", ["-ffp-contract=off"]),
+    ("guided.hip", ["-ffp-contract=off"]),
     ("edt.hip", ["-ffp-contract=off"]),
     ("memory_read.hip", []),
     ("memory_read_f16x3.hip", []),

@@ -17,6 +17,11 @@ are refused (as --viz is).
 labels/<stem>.png (8-bit grey: 0 bg, 128 unknown, 255 fg, anything else unlabelled) a correction of the propagated trimap; the
 clip is matted from the earliest trimap forward and then backward (video.keyframe_schedule), so its first frame needs no trimap.
 Without the flag those files are ignored.  Frames are decoded up front in this mode; refused with --batch > 1.
+--work-scale S (demo layout, S = 2, 3, 4): working-resolution matting -- the network runs on an S x S block mean of every frame and
+alpha (with --fgr / --composite also the foreground) returns to the input resolution through a guided filter on the frame itself
+(--work-radius R, --work-eps E: placeholders, not tuned on real footage; video.run_video_matte).  All PNGs keep the input
+resolution; works with --fgr, --composite and --keyframes; refused with --viz and --batch > 1.  The summary carries work_scale and
+work_size (per sequence).
 Frame IO runs through otvm_amd/io_pipeline.py: the demo flow decodes ahead in a thread pool and uploads on a copy
 stream, both flows download the 8-bit alphas asynchronously and PNG-encode them in a pool (the reference's loop blocks
 on .cpu() + cv2.imwrite per frame, eval.py:209-217).
@@ -60,6 +65,10 @@ def main(argv=None):
                     help="also write the foreground composited over a new background image or colour (<out>/comp/<seq>/)")
     ap.add_argument("--keyframes", action="store_true",
                     help="demo layout: use every trimap/<stem>.png as a full keyframe and every labels/<stem>.png as a correction")
+    ap.add_argument("--work-scale", type=int, default=None, choices=[2, 3, 4],
+                    help="demo layout: run the network on an S x S block mean of the frames, guided upsampling back to their resolution")
+    ap.add_argument("--work-radius", type=int, default=2, help="--work-scale: guided-filter radius in working pixels, 1 ... 4")
+    ap.add_argument("--work-eps", type=float, default=1e-4, help="--work-scale: guided-filter regulariser on the [0,1] scale")
     ap.add_argument("--max-frames", type=int, default=None, help="only the first N frames of every sequence")
     ap.add_argument("--weights", default=None)
     ap.add_argument("--synthetic-weights", action="store_true")
@@ -162,6 +171,10 @@ def main(argv=None):
     if args.keyframes and args.batch > 1:
         raise SystemExit("eval_cli: --batch %d steps clips in lock-step through matte_batch, which does not implement --keyframes"
                          % args.batch)
+    if args.work_scale is not None and not args.demo:
+        raise SystemExit("eval_cli: --work-scale belongs to the trimap (demo) flow; add --demo")
+    if args.work_scale is not None and (args.batch > 1 or args.viz):
+        raise SystemExit("eval_cli: --work-scale is a single-clip route without the --viz panels; drop --batch %d / --viz" % args.batch)
     if rank == 0:
         print("eval_cli: %d rank(s), lock-step batch %d per rank" % (world, args.batch))
     if distributed:
@@ -215,12 +228,19 @@ def main(argv=None):
                 Image.fromarray(u8.cpu().numpy()).save(os.path.join(outdir, data["names"][i] + ".png"))
             else:
                 writer.put(i, u8)
-            if fwriter is not None:
+            if fwriter is not None and args.work_scale is None:
                 fwriter.put(i, eng_of._engine.last_rgba_u8, bgr=bgr)
-            if cwriter is not None:
+            if cwriter is not None and args.work_scale is None:
                 cwriter.put(i, eng_of._engine.last_comp_u8, bgr=bgr)
             if args.viz:
                 viz.write_viz_frame(os.path.join(vizdir, "f%d.jpg" % i), out)
+        def save_full(i, rgba, comp):
+            # --work-scale: the engine's foreground bytes are at the working resolution; the full-resolution ones arrive here,
+            # frame by frame, and go to the writers as the others do
+            if fwriter is not None:
+                fwriter.put(i, rgba, bgr=bgr)
+            if cwriter is not None:
+                cwriter.put(i, comp, bgr=bgr)
         if demo:
             if args.sync_io or keyed:
                 frames, rgb, pre = data["frames"], False, None
@@ -233,9 +253,14 @@ def main(argv=None):
                 raise SystemExit("eval_cli: sequence %s has a trimap AND a label map for frame(s) %s" % (seq["name"], both))
             res = run_video_matte(model, frames, trimap=None if keyed else data["trimap"], skip=args.skip, max_num=args.max_num,
                                   on_frame=save, device=dev, frames_are_rgb=rgb, keep_on_device=True,
-                                  foreground=want_fgr, new_background=new_background(), keyframes=kf)
+                                  foreground=want_fgr, new_background=new_background(), keyframes=kf,
+                                  **(dict(work_scale=args.work_scale, work_radius=args.work_radius, work_eps=args.work_eps,
+                                          on_foreground=save_full if want_fgr else None)
+                                     if args.work_scale is not None else {}))
             if pre is not None:
                 pre.close()
+            if args.work_scale is not None:
+                res["work_scale"], res["work_size"] = args.work_scale, list(res["work_size"] or ())
         else:
             res = run_video_matte(model, data["frames"], alphas=data["alphas"], backgrounds=data["backgrounds"],
                                   skip=args.skip, max_num=args.max_num, on_frame=save, device=dev,
@@ -280,6 +305,10 @@ def main(argv=None):
     from .dist import reduce_device
     summary = run_sharded(seqs, matte, rank=rank, world=world, device=reduce_device(dev) if distributed else dev,
                           batch=max(1, args.batch), matte_batch_fn=matte_batch, key_fn=resolution)
+    if args.work_scale is not None:
+        # (the working sizes of the sequences this rank matted; a single-rank run lists them all)
+        summary["work_scale"] = args.work_scale
+        summary["work_size"] = {seqs[i]["name"]: o["work_size"] for i, o in summary["outputs"].items() if o.get("work_size")}
     if distributed:
         import torch.distributed as dist
         # which kernel configurations this rank launched (fp32 summation orders): identical on all ranks by construction

@@ -81,6 +81,12 @@ class FgrParams(C.Structure):
                 ("fgr", vp), ("rgba_u8", vp), ("comp_u8", vp), ("bg_u8", vp), ("bg_color", C.c_ubyte * 3), ("u8_rgb", i32)]
 
 
+class GuidedParams(C.Structure):
+    _fields_ = [("H", i32), ("W", i32), ("s", i32), ("h", i32), ("w", i32), ("r", i32), ("C", i32), ("eps", C.c_double),
+                ("guide_full", vp), ("guide_work", vp), ("target", vp * 4), ("coef", vp), ("alpha", vp), ("alpha_u8", vp),
+                ("fgr", vp)]
+
+
 class PpmHeadParams(C.Structure):
     _fields_ = [("pooled", vp), ("C", i32), ("K_pad", i32), ("Cout", i32),
                 ("w", vp * 4), ("bias", vp * 4), ("gamma", vp * 4), ("beta", vp * 4), ("out", vp * 4),
@@ -135,6 +141,12 @@ _PROTOS = {
     "otvm_fba_head": (i32, [vp, i32, vp, vp, i32, vp, i32, i64, vp, i32, vp, vp, i32, vp]),
     "otvm_fba_head_fgr": (i32, [vp, i32, vp, vp, i32, vp, i32, i64, vp, i32, vp, vp, i32, vp, vp]),
     "otvm_fgr_outputs": (i32, [C.POINTER(FgrParams), vp]),
+    "otvm_downsample_u8": (i32, [vp, i32, i32, i32, vp, vp]),
+    "otvm_downsample_trimap": (i32, [vp, i32, i32, i32, vp, vp]),
+    "otvm_downsample_labels": (i32, [vp, i32, i32, i32, vp, vp]),
+    "otvm_guided_ws_bytes": (i64, [i32, i32, i32]),
+    "otvm_guided_coeffs": (i32, [C.POINTER(GuidedParams), vp, vp]),
+    "otvm_guided_apply": (i32, [C.POINTER(GuidedParams), vp]),
     "otvm_crop_outputs": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "otvm_trimap_from_alpha": (i32, [vp, i32, i32, i32, vp, vp, vp]),
     "otvm_onehot_argmax3": (i32, [vp, i64, vp, vp]),

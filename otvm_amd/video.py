@@ -126,7 +126,7 @@ def _foreground_option(core, on):
 def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, skip=10, max_num=5,
                     frames_are_rgb=False, on_frame=None, device=None, keep_on_device=False, gt_alpha_u8=None,
                     gt_mask_u8=None, gt_mask=None, gt_image_metrics=False, gt_flow_metrics=False, foreground=False,
-                    new_background=None, keyframes=None):
+                    new_background=None, keyframes=None, work_scale=None, work_radius=2, work_eps=1e-4, on_foreground=None):
     """Matte one sequence.
 
     model       : EvalModel (optionally wrapped in nn.DataParallel), on the GPU
@@ -152,13 +152,44 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                   The clip is matted in the order of keyframe_schedule -- the keyframes, then forward from the earliest one,
                   then backward from it to frame 0 -- so ``frames`` must allow random access; on_frame fires in that order
                   with the frame's index.  Everything returned (and the metrics) is in natural frame order.
+    on_foreground : callable(i, rgba_u8 [H,W,4], comp_u8 [H,W,3] or None), fired per frame after on_frame when ``foreground`` is
+                  on.  The frames are then handed over instead of being collected: the result has no "fgr_u8" / "comp_u8" (a
+                  writer consumes them as they come; nothing of a long clip piles up on the device)
+    work_scale  : 2, 3 or 4: working-resolution matting.  The frames (uint8 [H,W,3] only) are reduced on the device to
+                  h x w = ceil(H / s) x ceil(W / s) by block means, the network runs there -- ``trimap`` and the entries of
+                  ``keyframes`` are given at H x W and reduced conservatively (otvm_amd/guided.py) -- and alpha (with ``foreground``
+                  also F) returns to H x W through a guided filter on the full-resolution frame of radius ``work_radius`` (1 ... 4,
+                  in working pixels) and regulariser ``work_eps`` ([0,1] scale).  The defaults of the two are PLACEHOLDERS: nobody
+                  has tuned them on real footage.  alpha, alpha_u8, fgr_u8, comp_u8, on_frame's alpha / u8 and the metrics are at
+                  H x W (``new_background`` too); ``trimap`` comes back at the working resolution [T,3,h,w], the result gains
+                  work_size=(h, w), and the memory schedule (large-input rule included) is evaluated at h x w, which is what the
+                  model runs.  Not available for float frames, the ``alphas`` flow, ``backgrounds`` or run_video_matte_batch.
     Returns dict(alpha=[T,H,W] float32, alpha_u8=[T,H,W] uint8 (truncated, eval.py:209), trimap=[T,3,H,W],
     bank_frames=[per frame: ids of the frames resident in the memory bank after that frame's update]) and, when ``keyframes``
     was given, anchor_frames=[per frame: those of them that are anchors], schedule=[the steps issued, keyframe_schedule's tuples].
     """
+    if work_scale is not None:
+        from . import guided
+        if work_scale not in guided.SCALES:
+            raise ValueError("run_video_matte: work_scale is 2, 3 or 4 (an integer scale), got %r" % (work_scale,))
+        if work_radius not in guided.RADII:
+            raise ValueError("run_video_matte: work_radius is 1 ... 4, got %r" % (work_radius,))
+        if not work_eps > 0:
+            raise ValueError("run_video_matte: work_eps must be positive, got %r" % (work_eps,))
+        if alphas is not None:
+            raise ValueError("run_video_matte: work_scale belongs to the trimap flow; the alphas flow (VideoMatting108: trimaps "
+                             "from ground-truth alpha) has no working-resolution route")
+        if backgrounds is not None:
+            raise ValueError("run_video_matte: work_scale takes no per-frame `backgrounds` (they belong to the alphas flow)")
     frames = list(frames) if not (hasattr(frames, "shape") or hasattr(frames, "__getitem__")) else frames
     T = len(frames)
     dev = device or next(model.parameters()).device
+    ups, work_hw = None, None
+    # (a plain sequence is checked before anything is uploaded; a streaming source is checked frame by frame below)
+    if (work_scale is not None and T > 0 and (isinstance(frames, (list, tuple, np.ndarray)) or torch.is_tensor(frames))
+            and _as_tensor(frames[0]).dtype != torch.uint8):
+        raise ValueError("run_video_matte: work_scale takes uint8 [H,W,3] frames (float frames have no working-resolution "
+                         "route), got %s" % _as_tensor(frames[0]).dtype)
     out_a, out_u8, out_t, bank_log, anchor_log = [None] * T, [None] * T, [None] * T, [None] * T, [None] * T
     out_f, out_c, bg_cache = [None] * T, [None] * T, {}
     core = model.module if hasattr(model, "module") else model
@@ -182,9 +213,14 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
     if keyframes is not None and T > 0:
         for t, v in keyframes.items():
             if _keyframe_kind(v) == "key":
-                tri_devs[t] = _as_tensor(v).to(dev).float()[None, None]
+                tri_devs[t] = _as_tensor(v).to(dev).float()
+                if work_scale is not None:
+                    tri_devs[t] = guided.downsample_trimap(tri_devs[t], work_scale)
+                tri_devs[t] = tri_devs[t][None, None]
             else:
                 lab_devs[t] = _as_tensor(v).to(dev)
+                if work_scale is not None:
+                    lab_devs[t] = guided.downsample_labels(lab_devs[t], work_scale)
         if not tri_devs:
             raise ValueError("run_video_matte: keyframes need at least one full trimap (one-hot [3,H,W])")
         k0 = min(tri_devs)
@@ -201,7 +237,22 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
             f = _as_tensor(frames[i])
             b = _as_tensor(backgrounds[i]) if backgrounds is not None else None
             extra = {}
-            if f.dtype == torch.uint8 and (b is None or b.dtype == torch.uint8):
+            if work_scale is not None:
+                if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != 3:
+                    raise ValueError("run_video_matte: work_scale takes uint8 [H,W,3] frames (float frames have no "
+                                     "working-resolution route), got %s %s" % (f.dtype, tuple(f.shape)))
+                ready = getattr(f, "_otvm_ready", None)
+                full = f.to(dev, non_blocking=True).contiguous()
+                if ready is not None:
+                    torch.cuda.current_stream(dev).wait_event(ready)     # the reduction below reads the upload on this stream
+                if ups is None or (ups.H, ups.W) != tuple(full.shape[:2]):
+                    ups = guided.GuidedUpsampler(dev, full.shape[0], full.shape[1], work_scale, work_radius, work_eps,
+                                                 4 if foreground else 1)
+                    work_hw = (ups.h, ups.w)
+                fg = bg = ups.reduce(full)
+                H, W = work_hw
+                extra["_frames_rgb"] = bool(frames_are_rgb)
+            elif f.dtype == torch.uint8 and (b is None or b.dtype == torch.uint8):
                 # decoded images go to the device as they are ([H,W,3] uint8): the preprocess kernel converts, flips the
                 # channel order and composites -- no per-frame torch conversion / transposition kernels
                 ready = getattr(f, "_otvm_ready", None)           # upload event of the IO pipeline's prefetcher
@@ -254,11 +305,24 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
             if step_memorize is not None:
                 memorize = step_memorize
             if foreground:
-                core.set_background(None if new_background is None else _background_at(new_background, i, dev, bg_cache))
+                # (working resolution: the composite is made at full resolution below, not by the engine)
+                core.set_background(None if new_background is None or ups is not None
+                                    else _background_at(new_background, i, dev, bg_cache))
             out = model(a, fg, bg, tri=None, tri_gt=tri_gt, first_frame=first_frame, last_frame=last_frame,
                         memorize=memorize, max_memory_num=max_memory_num, large_input=large, _frame_id=i, **extra)
             alpha = out[3][0, 0, 0]
             u8 = core._engine.last_alpha_u8
+            rgba = comp = None
+            if ups is not None:
+                # guided upsampling on this stream, behind the frame: the guide is the working frame the network saw
+                alpha, u8, fgr_full = ups.upsample(full, fg, [alpha] + (list(core._engine.last_fgr) if foreground else []))
+                if foreground:
+                    nb = None if new_background is None else _background_at(new_background, i, dev, bg_cache)
+                    if isinstance(nb, tuple) and not (len(nb) == 3 and all(0 <= int(x) <= 255 for x in nb)):
+                        raise ValueError("run_video_matte: a background colour is three values in 0..255, got %r" % (nb,))
+                    rgba, comp = ups.foreground_bytes(alpha, fgr_full, frames_are_rgb, nb)
+            elif foreground:
+                rgba, comp = core._engine.last_rgba_u8, core._engine.last_comp_u8
             mem_now = core.memories                                 # frame ids resident after this frame's update (host lists)
             bank_log[i], anchor_log[i] = list(mem_now["frames"]), list(mem_now["anchors"])
             if metrics is not None and natural:
@@ -269,11 +333,12 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                 out_a[i], out_u8[i], out_t[i] = alpha, u8, out[1][0, 0]
             else:
                 out_a[i], out_u8[i], out_t[i] = alpha.cpu(), u8.cpu(), out[1][0, 0].cpu()
-            if foreground:
-                eng = core._engine
-                out_f[i] = eng.last_rgba_u8 if keep_on_device else eng.last_rgba_u8.cpu()
+            if foreground and on_foreground is not None:
+                on_foreground(i, rgba, comp)
+            elif foreground:
+                out_f[i] = rgba if keep_on_device else rgba.cpu()
                 if new_background is not None:
-                    out_c[i] = eng.last_comp_u8 if keep_on_device else eng.last_comp_u8.cpu()
+                    out_c[i] = comp if keep_on_device else comp.cpu()
     if metrics is not None and not natural:
         # the pair terms (dtSSD, MESSDdt) depend on the order: fed in natural frame order from the kept 8-bit alphas
         for i in range(T):
@@ -281,7 +346,9 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
     res = dict(alpha=torch.stack(out_a), alpha_u8=torch.stack(out_u8), trimap=torch.stack(out_t), bank_frames=bank_log)
     if keyed:
         res.update(anchor_frames=anchor_log, schedule=list(steps or []))
-    if foreground:
+    if work_scale is not None:
+        res["work_size"] = work_hw
+    if foreground and on_foreground is None:
         res["fgr_u8"] = torch.stack(out_f)
         if new_background is not None:
             res["comp_u8"] = torch.stack(out_c)
@@ -300,7 +367,8 @@ def _metrics_add(metrics, u8, i, gt_alpha_u8, gt_mask_u8, gt_mask, dev):
 
 def run_video_matte_batch(model, clips, trimaps=None, alphas=None, backgrounds=None, skip=10, max_num=5, frames_are_rgb=False,
                           device=None, keep_on_device=False, on_frame=None, gt_alpha_u8=None, gt_mask=None,
-                          gt_image_metrics=False, gt_flow_metrics=False, foreground=False, new_background=None, keyframes=None):
+                          gt_image_metrics=False, gt_flow_metrics=False, foreground=False, new_background=None, keyframes=None,
+                          work_scale=None):
     """Matte B sequences of one resolution in LOCK-STEP (round 3): frame i of every clip goes through the network in one
     batched step (EvalModel.forward_batch: one launch per layer over the B images, per-sequence memory banks).
     clips: list of B frame arrays ([T_b,H,W,3] uint8 / float, BGR unless frames_are_rgb); trimaps: list of B first-frame
@@ -320,6 +388,9 @@ def run_video_matte_batch(model, clips, trimaps=None, alphas=None, backgrounds=N
     Returns a list of B dicts (alpha, alpha_u8, trimap, bank_frames[, metrics][, fgr_u8][, comp_u8])."""
     if keyframes is not None:
         raise NotImplementedError("run_video_matte_batch: keyframes are a single-clip feature (run_video_matte)")
+    if work_scale is not None:
+        raise ValueError("run_video_matte_batch: work_scale (working-resolution matting) is a single-clip feature "
+                         "(run_video_matte); lock-step batches run at the frames' resolution")
     B = len(clips)
     lens = [len(c) for c in clips]
     T = max(lens)
