@@ -67,7 +67,8 @@ const char* otvm_last_error(void);
                                   caller built against the earlier 21 runs unchanged and the number stays;
                                   likewise otvm_trimap_apply_labels, the label pass of the keyframe corrections;
                                   likewise working-resolution matting: otvm_downsample_u8 / _trimap / _labels, otvm_guided_ws_bytes,
-                                  otvm_guided_coeffs and otvm_guided_apply with their struct otvm_guided_params) */
+                                  otvm_guided_coeffs and otvm_guided_apply with their struct otvm_guided_params;
+                                  likewise trimaps from masks: otvm_trimap_from_mask / _ws_bytes with otvm_mask_trimap_params) */
 int otvm_abi_version(void);
 
 /* ---------------------------------------------------------------- weights (load time) ----------
@@ -542,6 +543,33 @@ int otvm_guided_apply(const otvm_guided_params* p, void* stream);
 /* first-frame trimap from a GT alpha (alpha/model.py:342-362): unknown = dilate(0<a<1) with a
  * (2r+1)^2 max filter, fg = (a==1), bg = (a==0); out planar one-hot [3,H,W]; ws >= H*W bytes      */
 int otvm_trimap_from_alpha(const float* a, int H, int W, int r, float* out, void* ws, void* stream);
+
+/* Trimap from a segmentation mask: exact erosion of the thresholded mask by Euclidean discs (an extension; the reference
+ * derives trimaps from ground-truth alpha only, which gives a binary mask no unknown band).  Integers throughout.
+ *   FG = (m >= hi), BG = (m <= lo) for the mask m, uint8 [H,W], 0 <= lo < hi <= 255;
+ *   d_S(p) = min over the in-image pixels q not in S of |p - q|^2 (an exact integer; +inf when every pixel is in S).  Pixels
+ *   outside the image belong to no set and seed nothing: a subject cut by the frame edge stays foreground up to the edge;
+ *   fg = FG and d_FG > t_fg, bg = BG and d_BG > t_bg, everything else is unknown.  t = floor(r^2) for a band of r pixels,
+ *   r = 0 ... 255; t = 0 gives the thresholded mask (unknown only where lo < m < hi).
+ * Only the comparison with t matters, so with R = floor(sqrt(t)) the search is bounded: the vertical distance g to the nearest
+ * non-member of the pixel's column, capped (any cap above R serves: 256 here), then per row the minimum over |dx| <= R of
+ * g^2 + dx^2.  Two launches, no atomics (two calls give equal bits), nothing launched when an argument is refused.
+ *   trimap : planar one-hot [3,H,W] (bg, unknown, fg), the layout of otvm_trimap_from_alpha's output, or NULL;
+ *   labels : uint8 [H,W], 0 bg, 2 fg and band_label elsewhere -- 1 (unknown) or 255 (unlabelled: what
+ *            otvm_trimap_apply_labels leaves alone, so a propagated trimap survives in the band) -- or NULL; one of the two
+ *            outputs at least;
+ *   ws     : otvm_trimap_from_mask_ws_bytes(H, W) bytes, 2-byte aligned, no initialisation; one ws serves one stream at a time.
+ * New symbols only (additive, as the entries above): the ABI number stays.                                                   */
+typedef struct otvm_mask_trimap_params {
+    const uint8_t* mask;      /* [H,W] */
+    int H, W, lo, hi;         /* 1 <= H, W < 16384; 0 <= lo < hi <= 255 */
+    int t_fg, t_bg;           /* 0 .. 65025 */
+    float* trimap;            /* planar one-hot [3,H,W] (bg, unknown, fg), or NULL */
+    uint8_t* labels;          /* [H,W]: 0 bg, 2 fg, band_label elsewhere, or NULL */
+    int band_label;           /* 1 (unknown) or 255 (unlabelled) */
+} otvm_mask_trimap_params;
+int64_t otvm_trimap_from_mask_ws_bytes(int H, int W);      /* -1 for bad sizes */
+int otvm_trimap_from_mask(const otvm_mask_trimap_params* p, void* ws, void* stream);
 
 /* one-hot of the argmax of a planar [3,H,W] trimap (alpha/model.py:356-362, returned tri_gt) */
 int otvm_onehot_argmax3(const float* tri, int64_t P, float* out, void* stream);

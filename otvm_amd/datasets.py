@@ -9,7 +9,8 @@ Mirrors the iteration protocol of the reference so a loop written against it kee
             path is repeated for later frames; '' before the first one).  The reference's model consumes the first
             frame's trimap only; load_sequence(keyframes=True) also returns every later frame's own trimap, and the
             label maps <root>/<seq>/labels/<frame stem>.png (8-bit grey: 0 bg, 128 unknown, 255 fg, any other value
-            unlabelled) -- what run_video_matte(keyframes=...) takes
+            unlabelled) -- what run_video_matte(keyframes=...) takes; load_sequence(masks=True) the segmentation masks
+            <root>/<seq>/mask/<frame stem>.png (8-bit grey) -- what run_video_matte(mask= / masks= / keyframes=Mask) takes
     V108  : <root>/VideoMatting108/{frame_corr.json, val_videos.txt, FG_done/<video>/<clip>/*.png (RGBA),
             BG_done2/...}; frame_corr maps an FG frame to its BG frame; a video's frames are the sorted keys of
             frame_corr whose dirname is the line of the set file
@@ -158,7 +159,12 @@ def read_label_map(path):
     return out
 
 
-def load_sequence(item, max_frames=None, decode_frames=True, keyframes=False):
+def read_mask(path):
+    """mask/<stem>.png -> uint8 [H,W], the grey levels as they are (a colour or 16-bit file is converted to 8-bit grey)."""
+    return np.ascontiguousarray(_imread(path, "L"))
+
+
+def load_sequence(item, max_frames=None, decode_frames=True, keyframes=False, masks=False):
     """Decode one item of either iterator into what run_video_matte takes.
 
     Returns dict(name, names=[file stems], frames=[uint8 BGR], and either trimap=one-hot [3,H,W] (demo) or
@@ -166,6 +172,8 @@ def load_sequence(item, max_frames=None, decode_frames=True, keyframes=False):
     keyframes (demo layout): also keyframe_trimaps={frame index: one-hot [3,H,W]} of every frame that has a trimap file of
     its own and label_maps={frame index: uint8 [H,W]} of every frame with a labels/<stem>.png; the first frame then needs no
     trimap (``trimap`` is None without one) as long as some frame has.
+    masks (demo layout): also mask_maps={frame index: uint8 [H,W]} of every frame with a mask/<stem>.png.  A clip without any
+    trimap file is then no error here (``trimap`` is None, ``keyframe_trimaps`` empty): the caller knows what its route needs.
     """
     from .video import trimap_file_to_onehot
     data_name, root, FG, BG, _a, TRI, seq_name = item
@@ -179,10 +187,16 @@ def load_sequence(item, max_frames=None, decode_frames=True, keyframes=False):
         # frame's: a clip whose FIRST frame has no trimap file cannot be evaluated (cv2.imread('') -> None there)
         tri = TRI[0] if TRI else ""
         out["frame_paths"] = [os.path.join(root, p) for p in FG[:n]]
+        if masks:
+            out["mask_maps"] = {}
+            for t in range(n):
+                mp = os.path.join(root, seq_name, "mask", names[t] + ".png")
+                if os.path.isfile(mp):
+                    out["mask_maps"][t] = read_mask(mp)
         if keyframes:
             # a frame's own trimap: the listed path carries the frame's stem (later frames repeat the most recent path)
             own = {t: TRI[t] for t in range(n) if TRI[t] and os.path.splitext(os.path.basename(TRI[t]))[0] == names[t]}
-            if not own:
+            if not own and not masks:
                 raise FileNotFoundError("sequence %s: no trimap for any of its %d frames (%s/%s/trimap/<frame>.png)"
                                         % (seq_name, n, root, seq_name))
             out["keyframe_trimaps"] = {t: trimap_file_to_onehot(read_trimap_unchanged(os.path.join(root, p)))
@@ -193,6 +207,9 @@ def load_sequence(item, max_frames=None, decode_frames=True, keyframes=False):
                 lp = os.path.join(root, seq_name, "labels", names[t] + ".png")
                 if os.path.isfile(lp):
                     out["label_maps"][t] = read_label_map(lp)
+            return out
+        if not tri and masks:
+            out["trimap"] = None
             return out
         if not tri:
             raise FileNotFoundError("sequence %s: no trimap for its first frame (%s/%s/trimap/%s.png)"

@@ -22,6 +22,14 @@ alpha (with --fgr / --composite also the foreground) returns to the input resolu
 (--work-radius R, --work-eps E: placeholders, not tuned on real footage; video.run_video_matte).  All PNGs keep the input
 resolution; works with --fgr, --composite and --keyframes; refused with --viz and --batch > 1.  The summary carries work_scale and
 work_size (per sequence).
+--masks key|frame (demo layout): trimaps from segmentation masks, mask/<stem>.png (8-bit grey), made on the device
+(otvm_amd/masks.py).  key: every mask file is a full keyframe, as a trimap file is under --keyframes; a clip needs a trimap or a
+mask on at least one frame (without --keyframes only the first frame's trimap file counts).  frame: every frame needs a mask and
+is matted from it alone, nothing is propagated (run_video_matte(masks=...)).  --mask-band R[,R_BG] is the reach of the unknown
+band into the foreground / background in pixels (default: the --trimap dilation), --mask-thresholds LO,HI the cut (foreground
+>= HI, background <= LO; default 127,128) -- placeholders, not tuned on real footage.  Works with --fgr, --composite, --work-scale
+and, in key mode, --keyframes (labels/ too); refused with --batch > 1 and without --demo.  The summary carries masks, mask_band
+and mask_thresholds.
 Frame IO runs through otvm_amd/io_pipeline.py: the demo flow decodes ahead in a thread pool and uploads on a copy
 stream, both flows download the 8-bit alphas asynchronously and PNG-encode them in a pool (the reference's loop blocks
 on .cpu() + cv2.imwrite per frame, eval.py:209-217).
@@ -53,6 +61,27 @@ def parse_composite(spec):
     return None, spec
 
 
+def parse_mask_options(band, thresholds):
+    """--mask-band "R[,R_BG]" -> r | (r_fg, r_bg) | None, --mask-thresholds "LO,HI" -> (lo, hi); both checked as masks.Mask does."""
+    from .masks import band_thresholds, check_thresholds
+    try:
+        b = None
+        if band is not None:
+            parts = [float(x) for x in band.split(",")]
+            if len(parts) not in (1, 2):
+                raise ValueError("one or two radii")
+            b = parts[0] if len(parts) == 1 else tuple(parts)
+            band_thresholds(b)
+    except ValueError as e:
+        raise SystemExit("eval_cli: --mask-band is R or R,R_BG with radii in 0 ... 255 pixels, got %r (%s)" % (band, e))
+    try:
+        lo, hi = (int(x) for x in thresholds.split(","))
+        check_thresholds(lo, hi)
+    except ValueError as e:
+        raise SystemExit("eval_cli: --mask-thresholds is LO,HI with 0 <= LO < HI <= 255, got %r (%s)" % (thresholds, e))
+    return b, (lo, hi)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--data", required=True)
@@ -69,6 +98,13 @@ def main(argv=None):
                     help="demo layout: run the network on an S x S block mean of the frames, guided upsampling back to their resolution")
     ap.add_argument("--work-radius", type=int, default=2, help="--work-scale: guided-filter radius in working pixels, 1 ... 4")
     ap.add_argument("--work-eps", type=float, default=1e-4, help="--work-scale: guided-filter regulariser on the [0,1] scale")
+    ap.add_argument("--masks", default=None, choices=["key", "frame"],
+                    help="demo layout: trimaps from the segmentation masks mask/<stem>.png; key = every mask is a full keyframe, "
+                         "frame = every frame is matted from its own mask, nothing propagated")
+    ap.add_argument("--mask-band", default=None, metavar="R[,R_BG]",
+                    help="--masks: reach of the unknown band into foreground / background in pixels (default: the --trimap dilation)")
+    ap.add_argument("--mask-thresholds", default="127,128", metavar="LO,HI",
+                    help="--masks: foreground is mask >= HI, background mask <= LO (8-bit scale)")
     ap.add_argument("--max-frames", type=int, default=None, help="only the first N frames of every sequence")
     ap.add_argument("--weights", default=None)
     ap.add_argument("--synthetic-weights", action="store_true")
@@ -97,6 +133,15 @@ def main(argv=None):
     from .video import run_video_matte
 
     comp_color, comp_image = parse_composite(args.composite)
+    mask_band, (mask_lo, mask_hi) = parse_mask_options(args.mask_band, args.mask_thresholds)
+    if args.masks and not args.demo:
+        raise SystemExit("eval_cli: --masks reads the demo layout's mask/ folder; add --demo")
+    if args.masks and args.batch is not None and args.batch > 1:
+        raise SystemExit("eval_cli: --batch %d steps clips in lock-step through matte_batch, which does not implement --masks"
+                         % args.batch)
+    if args.masks == "frame" and args.keyframes:
+        raise SystemExit("eval_cli: --masks frame mattes every frame from its own mask and propagates nothing: there is no trimap "
+                         "for --keyframes to place or correct; use --masks key")
 
     if args.gpus is not None and args.gpus > 1 and "RANK" not in os.environ:
         import subprocess
@@ -155,7 +200,7 @@ def main(argv=None):
         # (--viz and --sync-io are single-clip features -- matte_batch writes no viz frames and decodes every clip of a group up
         #  front -- so they keep batch 1 unless --batch is given explicitly)
         if world > 1 and any(k is not None for k in keys) and not (args.viz or args.sync_io or args.fgr or args.composite
-                                                                   or args.keyframes):
+                                                                   or args.keyframes or args.masks):
             def padded(k):
                 lw, uw, lh, uh = pad_amounts(k[0], k[1], 32)
                 return (k[0] + lh + uh) * (k[1] + lw + uw)
@@ -194,9 +239,9 @@ def main(argv=None):
 
     def matte(seq):
         demo = seq["item"][0] == "demo"
-        keyed = demo and args.keyframes                     # frames in schedule order: decoded up front, not prefetched
+        keyed = demo and (args.keyframes or args.masks == "key")   # frames in schedule order: decoded up front, not prefetched
         data = datasets.load_sequence(seq["item"], max_frames=args.max_frames, decode_frames=not demo or args.sync_io or keyed,
-                                      keyframes=keyed)
+                                      keyframes=demo and args.keyframes, masks=demo and bool(args.masks))
         outdir = os.path.join(root_out, "pred", seq["name"])
         os.makedirs(outdir, exist_ok=True)
         vizdir = os.path.join(args.out, "viz", "test", helpers.get_model_name(cfg), "viz", seq["name"])
@@ -247,11 +292,33 @@ def main(argv=None):
             else:                                  # decode ahead + pinned upload on a copy stream (RGB order)
                 pre = FramePrefetcher(data["frame_paths"], dev)
                 frames, rgb = _Listish(pre), True
-            kf = {**data["keyframe_trimaps"], **data["label_maps"]} if keyed else None
-            both = keyed and sorted(set(data["keyframe_trimaps"]) & set(data["label_maps"]))
+            kf = {**data["keyframe_trimaps"], **data["label_maps"]} if args.keyframes else ({} if keyed else None)
+            both = args.keyframes and sorted(set(data["keyframe_trimaps"]) & set(data["label_maps"]))
             if both:
                 raise SystemExit("eval_cli: sequence %s has a trimap AND a label map for frame(s) %s" % (seq["name"], both))
-            res = run_video_matte(model, frames, trimap=None if keyed else data["trimap"], skip=args.skip, max_num=args.max_num,
+            per_frame = None
+            if args.masks:
+                from .masks import Mask
+                mk = {t: Mask(m, band=mask_band, lo=mask_lo, hi=mask_hi) for t, m in data["mask_maps"].items()}
+                if args.masks == "frame":
+                    missing = [n for t, n in enumerate(data["names"]) if t not in mk]
+                    if missing:
+                        raise SystemExit("eval_cli: --masks frame needs a mask for every frame; sequence %s has none for %s"
+                                         % (seq["name"], ", ".join(missing[:5]) + (" ..." if len(missing) > 5 else "")))
+                    per_frame = [mk[t] for t in range(len(data["names"]))]
+                else:
+                    if not args.keyframes and data["trimap"] is not None:
+                        kf[0] = data["trimap"]               # (without --keyframes only the first frame's trimap file counts)
+                    both = sorted(set(kf) & set(mk))
+                    if both:
+                        raise SystemExit("eval_cli: sequence %s has a mask AND a trimap or label map for frame(s) %s"
+                                         % (seq["name"], both))
+                    kf.update(mk)
+                    if not (mk or (data["keyframe_trimaps"] if args.keyframes else data["trimap"] is not None)):
+                        raise SystemExit("eval_cli: sequence %s has neither a trimap nor a mask on any frame (%s/%s/trimap|mask/"
+                                         "<frame>.png)" % (seq["name"], seq["item"][1], seq["name"]))
+            res = run_video_matte(model, frames, trimap=None if (keyed or per_frame is not None) else data["trimap"], skip=args.skip,
+                                  max_num=args.max_num, masks=per_frame,
                                   on_frame=save, device=dev, frames_are_rgb=rgb, keep_on_device=True,
                                   foreground=want_fgr, new_background=new_background(), keyframes=kf,
                                   **(dict(work_scale=args.work_scale, work_radius=args.work_radius, work_eps=args.work_eps,
@@ -309,6 +376,10 @@ def main(argv=None):
         # (the working sizes of the sequences this rank matted; a single-rank run lists them all)
         summary["work_scale"] = args.work_scale
         summary["work_size"] = {seqs[i]["name"]: o["work_size"] for i, o in summary["outputs"].items() if o.get("work_size")}
+    if args.masks:
+        summary["masks"] = args.masks
+        summary["mask_band"] = list(mask_band) if isinstance(mask_band, tuple) else [dk if mask_band is None else mask_band] * 2
+        summary["mask_thresholds"] = [mask_lo, mask_hi]
     if distributed:
         import torch.distributed as dist
         # which kernel configurations this rank launched (fp32 summation orders): identical on all ranks by construction

@@ -87,6 +87,11 @@ class GuidedParams(C.Structure):
                 ("fgr", vp)]
 
 
+class MaskTrimapParams(C.Structure):
+    _fields_ = [("mask", vp), ("H", i32), ("W", i32), ("lo", i32), ("hi", i32), ("t_fg", i32), ("t_bg", i32),
+                ("trimap", vp), ("labels", vp), ("band_label", i32)]
+
+
 class PpmHeadParams(C.Structure):
     _fields_ = [("pooled", vp), ("C", i32), ("K_pad", i32), ("Cout", i32),
                 ("w", vp * 4), ("bias", vp * 4), ("gamma", vp * 4), ("beta", vp * 4), ("out", vp * 4),
@@ -149,6 +154,8 @@ _PROTOS = {
     "otvm_guided_apply": (i32, [C.POINTER(GuidedParams), vp]),
     "otvm_crop_outputs": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "otvm_trimap_from_alpha": (i32, [vp, i32, i32, i32, vp, vp, vp]),
+    "otvm_trimap_from_mask_ws_bytes": (i64, [i32, i32]),
+    "otvm_trimap_from_mask": (i32, [C.POINTER(MaskTrimapParams), vp, vp]),
     "otvm_onehot_argmax3": (i32, [vp, i64, vp, vp]),
     "otvm_matting_metrics": (i32, [vp, vp, vp, vp, vp, vp, i64, vp, vp]),
     "otvm_matting_grad_conn": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp]),

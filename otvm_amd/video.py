@@ -9,6 +9,8 @@ import contextlib
 import numpy as np
 import torch
 
+from .masks import Mask, as_mask
+
 
 def memory_schedule(i_seq, height, width, skip=10, max_num=5):
     """(memorize, max_memory_num, large_input) for frame ``i_seq`` -- eval.py:180-190, config.py:22-23."""
@@ -21,6 +23,8 @@ def memory_schedule(i_seq, height, width, skip=10, max_num=5):
 
 def _keyframe_kind(v):
     """"key" (a full trimap: one-hot [3,H,W]) or "labels" (a uint8 [H,W] label map) of one entry of ``keyframes``."""
+    if isinstance(v, Mask):                           # a mask in a trimap's ("key") or a label map's ("labels") place
+        return v.role
     if isinstance(v, str):
         if v not in ("key", "labels"):
             raise ValueError("keyframes: an entry is a one-hot trimap [3,H,W], a uint8 label map [H,W], 'key' or 'labels'; got %r" % v)
@@ -126,7 +130,8 @@ def _foreground_option(core, on):
 def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, skip=10, max_num=5,
                     frames_are_rgb=False, on_frame=None, device=None, keep_on_device=False, gt_alpha_u8=None,
                     gt_mask_u8=None, gt_mask=None, gt_image_metrics=False, gt_flow_metrics=False, foreground=False,
-                    new_background=None, keyframes=None, work_scale=None, work_radius=2, work_eps=1e-4, on_foreground=None):
+                    new_background=None, keyframes=None, work_scale=None, work_radius=2, work_eps=1e-4, on_foreground=None,
+                    mask=None, masks=None):
     """Matte one sequence.
 
     model       : EvalModel (optionally wrapped in nn.DataParallel), on the GPU
@@ -164,6 +169,18 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                   H x W (``new_background`` too); ``trimap`` comes back at the working resolution [T,3,h,w], the result gains
                   work_size=(h, w), and the memory schedule (large-input rule included) is evaluated at h x w, which is what the
                   model runs.  Not available for float frames, the ``alphas`` flow, ``backgrounds`` or run_video_matte_batch.
+    mask        : a segmentation mask of the first frame in ``trimap``'s place: an array / tensor [H,W] (uint8, or float in
+                  [0,1]; binary or soft) or a masks.Mask carrying its band and thresholds.  The trimap is made on the device
+                  (otvm_trimap_from_mask: the thresholded mask eroded by exact Euclidean discs; the band defaults to the model's
+                  DILATION_KERNEL, the thresholds to a binary cut -- PLACEHOLDERS nobody tuned on real footage).  The entries of
+                  ``keyframes`` may be Masks too: role="key" a full keyframe, role="labels" a correction whose band stays
+                  unlabelled.  Every mask is converted once per clip, at H x W (before the reduction of ``work_scale``); the band
+                  is in full-resolution pixels.
+    masks       : one mask per frame (a sequence of T arrays or Masks, role "key"): every frame is matted from its own mask and
+                  NOTHING is propagated -- each step runs as a clip of one frame (first_frame and last_frame), in natural order,
+                  so the STM query encoder, memory read, decoder and Encoder_M never run and the bank stays empty (bank_frames
+                  is [] for every frame).  Exclusive with trimap, mask, keyframes and alphas; on_frame, the metrics, foreground
+                  and new_background work as in any clip.  Not available in run_video_matte_batch.
     Returns dict(alpha=[T,H,W] float32, alpha_u8=[T,H,W] uint8 (truncated, eval.py:209), trimap=[T,3,H,W],
     bank_frames=[per frame: ids of the frames resident in the memory bank after that frame's update]) and, when ``keyframes``
     was given, anchor_frames=[per frame: those of them that are anchors], schedule=[the steps issued, keyframe_schedule's tuples].
@@ -184,6 +201,31 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
     frames = list(frames) if not (hasattr(frames, "shape") or hasattr(frames, "__getitem__")) else frames
     T = len(frames)
     dev = device or next(model.parameters()).device
+    mask_hw = {}                                      # frame -> the size of the mask it was given (checked against the frame)
+    if mask is not None or masks is not None:
+        if masks is not None:
+            for name, other in (("trimap", trimap), ("mask", mask), ("keyframes", keyframes), ("alphas", alphas)):
+                if other is not None:
+                    raise ValueError("run_video_matte: `masks` mattes every frame from its own mask and excludes `%s`" % name)
+            masks = [as_mask(m, "run_video_matte: masks[%d]" % j) for j, m in enumerate(masks)]
+            if len(masks) != T:
+                raise ValueError("run_video_matte: `masks` needs one mask per frame, got %d for %d frames" % (len(masks), T))
+            if any(m.role != "key" for m in masks):
+                raise ValueError("run_video_matte: a Mask of `masks` has role 'key' (role='labels' corrects a PROPAGATED trimap; "
+                                 "nothing is propagated here)")
+            for m in masks:
+                m.band_for(model)                         # (a missing band is refused before any frame runs)
+        if mask is not None:
+            if trimap is not None:
+                raise ValueError("run_video_matte: frame 0 has both `trimap` and `mask`")
+            if alphas is not None:
+                raise ValueError("run_video_matte: `mask` belongs to the trimap flow (no per-frame alphas)")
+            if keyframes is not None and 0 in {int(t) for t in keyframes}:
+                raise ValueError("run_video_matte: frame 0 has both `mask` and an entry of `keyframes`")
+            trimap = as_mask(mask, "run_video_matte: mask")
+            if trimap.role != "key":
+                raise ValueError("run_video_matte: `mask` is the first frame's trimap: a Mask with role 'key' (role='labels' "
+                                 "corrects a propagated trimap on a later frame)")
     ups, work_hw = None, None
     # (a plain sequence is checked before anything is uploaded; a streaming source is checked frame by frame below)
     if (work_scale is not None and T > 0 and (isinstance(frames, (list, tuple, np.ndarray)) or torch.is_tensor(frames))
@@ -209,6 +251,12 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
             keyframes[0] = trimap
     elif trimap is not None:
         keyframes = {0: trimap}
+    if keyframes is not None and T > 0:
+        # masks become ordinary trimaps / label maps here, once per clip, at the resolution they were given
+        for t, v in list(keyframes.items()):
+            if isinstance(v, Mask):
+                mask_hw[t] = v.shape
+                keyframes[t] = v.convert(model, dev)
     tri_devs, lab_devs, steps, k0 = {}, {}, None, 0
     if keyframes is not None and T > 0:
         for t, v in keyframes.items():
@@ -228,6 +276,9 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
         large = memory_schedule(0, tri_devs[k0].shape[-2], tri_devs[k0].shape[-1], skip, max_num)[2]
         steps = keyframe_schedule(T, {t: "key" for t in tri_devs} | {t: "labels" for t in lab_devs},
                                   int(skip * 2) if large else skip)
+    elif masks is not None and T > 0:
+        steps = [(i, "key", True, True, False) for i in range(T)]                   # T clips of one frame: nothing to memorise
+        mask_hw = {i: m.shape for i, m in enumerate(masks)}
     elif T > 0:
         steps = [(i, "frame", i == 0, i == T - 1, None) for i in range(T)]          # alpha flow: eval.py's loop as it is
     natural = steps is None or all(st[0] == j for j, st in enumerate(steps))
@@ -251,6 +302,7 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                     work_hw = (ups.h, ups.w)
                 fg = bg = ups.reduce(full)
                 H, W = work_hw
+                full_hw = tuple(full.shape[:2])
                 extra["_frames_rgb"] = bool(frames_are_rgb)
             elif f.dtype == torch.uint8 and (b is None or b.dtype == torch.uint8):
                 # decoded images go to the device as they are ([H,W,3] uint8): the preprocess kernel converts, flips the
@@ -261,6 +313,7 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                 if b is not None and getattr(b, "_otvm_ready", None) is not None:
                     torch.cuda.current_stream(dev).wait_event(b._otvm_ready)
                 H, W = fg.shape[:2]
+                full_hw = (H, W)
                 extra["_frames_rgb"] = bool(frames_are_rgb)
                 if ready is not None:
                     # the upload event may only travel to the model (whose query-encoder stream then starts on it, ahead of the
@@ -285,7 +338,21 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                     bg = b.permute(2, 0, 1)[None, None].contiguous()
                 else:
                     bg = fg
-            if keyframes is not None:
+                full_hw = (H, W)
+            # masks of a keyframe clip are all held against the first frame that comes by, those of `masks` each against its own
+            for t in ([i] if masks is not None else list(mask_hw)):
+                hw = mask_hw.pop(t)
+                if tuple(hw) != tuple(full_hw):
+                    raise ValueError("run_video_matte: the mask of frame %d is %dx%d, the frames are %dx%d (masks are given at "
+                                     "the frames' resolution)" % (t, hw[0], hw[1], full_hw[0], full_hw[1]))
+            if masks is not None:
+                if ones is None or ones.shape[-2:] != (H, W):
+                    ones = torch.ones(1, 1, 1, H, W, device=dev)
+                tri_gt = masks[i].convert(model, dev)             # this frame's own trimap; nothing is kept of it
+                if work_scale is not None:
+                    tri_gt = guided.downsample_trimap(tri_gt, work_scale)
+                a, tri_gt = ones, tri_gt[None, None]
+            elif keyframes is not None:
                 if ones is None or ones.shape[-2:] != (H, W):
                     ones = torch.ones(1, 1, 1, H, W, device=dev)
                 # (as eval.py does, every frame is handed a trimap -- it comes back as out[2]; only a keyframe consumes it)
@@ -368,7 +435,7 @@ def _metrics_add(metrics, u8, i, gt_alpha_u8, gt_mask_u8, gt_mask, dev):
 def run_video_matte_batch(model, clips, trimaps=None, alphas=None, backgrounds=None, skip=10, max_num=5, frames_are_rgb=False,
                           device=None, keep_on_device=False, on_frame=None, gt_alpha_u8=None, gt_mask=None,
                           gt_image_metrics=False, gt_flow_metrics=False, foreground=False, new_background=None, keyframes=None,
-                          work_scale=None):
+                          work_scale=None, mask=None, masks=None):
     """Matte B sequences of one resolution in LOCK-STEP (round 3): frame i of every clip goes through the network in one
     batched step (EvalModel.forward_batch: one launch per layer over the B images, per-sequence memory banks).
     clips: list of B frame arrays ([T_b,H,W,3] uint8 / float, BGR unless frames_are_rgb); trimaps: list of B first-frame
@@ -391,6 +458,9 @@ def run_video_matte_batch(model, clips, trimaps=None, alphas=None, backgrounds=N
     if work_scale is not None:
         raise ValueError("run_video_matte_batch: work_scale (working-resolution matting) is a single-clip feature "
                          "(run_video_matte); lock-step batches run at the frames' resolution")
+    if mask is not None or masks is not None or (trimaps is not None and any(isinstance(t, Mask) for t in trimaps)):
+        raise ValueError("run_video_matte_batch: trimaps from masks (mask / masks / a Mask) are a single-clip feature "
+                         "(run_video_matte); lock-step batches take trimaps")
     B = len(clips)
     lens = [len(c) for c in clips]
     T = max(lens)
