@@ -64,3 +64,19 @@ def conv2d(x, cw, out, bias=None, stride=1, pad=0, dil=1, act=0, in_relu=0, resi
 
 def maxdiff(a, b):
     return float((a - b).abs().max())
+
+
+def best_gbps(launch, nbytes, reps=5):
+    """Bytes the kernel has to move over the shortest of `reps` device-event timings of launch() (after two warm-up launches)."""
+    for _ in range(2):
+        launch()
+    torch.cuda.synchronize()
+    best = float("inf")
+    for _ in range(reps):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        launch()
+        t1.record()
+        t1.synchronize()
+        best = min(best, t0.elapsed_time(t1))
+    return nbytes / (best * 1e-3) / 1e9

@@ -477,6 +477,30 @@ def test_uint8_frames_equal_float_frames(model, synth_sd, rgb):
     assert not torch.equal(v_u8["alpha"], r_u8["alpha"])
 
 
+def test_rgb_uint8_frames_equal_the_same_clip_in_bgr(model, synth_sd):
+    """The same clip handed over as RGB bytes (frames_are_rgb=True) and as BGR bytes (False) gives the same alpha and trimap bits,
+    with a propagated trimap and with given alphas over separate backgrounds: the two channel orders are held against each
+    other, not each against itself."""
+    from otvm_amd.synth_data import soft_alpha, synthetic_clip
+    from otvm_amd.video import run_video_matte
+    H, W, T = 72, 104, 4
+    frames_bgr, tri = synthetic_clip(H, W, T, seed=51)
+    bgs_bgr, _ = synthetic_clip(H, W, T, seed=52)
+    m = model(12).module
+    rev = lambda lst: [f[..., ::-1].copy() for f in lst]
+    assert any((f[..., 0] != f[..., 2]).any() for f in frames_bgr)          # a swap of the outer channels changes the input
+    r_bgr = run_video_matte(m, frames_bgr, trimap=tri, skip=2, max_num=3, frames_are_rgb=False)
+    r_rgb = run_video_matte(m, rev(frames_bgr), trimap=tri, skip=2, max_num=3, frames_are_rgb=True)
+    assert torch.equal(r_rgb["alpha"], r_bgr["alpha"]) and torch.equal(r_rgb["trimap"], r_bgr["trimap"])
+    al = [soft_alpha(H, W, t) for t in range(T)]
+    v_bgr = run_video_matte(m, frames_bgr, alphas=al, backgrounds=bgs_bgr, skip=2, max_num=3, frames_are_rgb=False)
+    v_rgb = run_video_matte(m, rev(frames_bgr), alphas=al, backgrounds=rev(bgs_bgr), skip=2, max_num=3, frames_are_rgb=True)
+    assert torch.equal(v_rgb["alpha"], v_bgr["alpha"]) and torch.equal(v_rgb["trimap"], v_bgr["trimap"])
+    # the flag is what decides: the reversed bytes read as BGR are another clip
+    wrong = run_video_matte(m, rev(frames_bgr), trimap=tri, skip=2, max_num=3, frames_are_rgb=False)
+    assert not torch.equal(wrong["alpha"], r_bgr["alpha"])
+
+
 def test_same_padded_size_different_input_size_does_not_share_slots(model, synth_sd):
     """Two clips whose frames pad to the same size (208x88 and 203x77 -> 224x96) matted back to back by ONE module: the
     second must equal what a fresh module gives (bank slots carry launch parameters bound to a plan's buffers and may not
