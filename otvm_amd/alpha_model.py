@@ -13,6 +13,14 @@ from .engine import HipEngine
 from .modules import attach_from_spec
 
 
+def background_colour(bg, who="otvm_amd"):
+    """The rule for a colour to composite over: three values in 0..255 (``who`` names the caller in the refusal)."""
+    c = tuple(int(x) for x in bg)
+    if len(c) != 3 or not all(0 <= x <= 255 for x in c):
+        raise ValueError("%s: a background colour is three values in 0..255, got %r" % (who, bg))
+    return c
+
+
 class EvalModel(nn.Module):
     def __init__(self, dilate_kernel=None, eps=0, trimap=None, stage=1):
         super().__init__()
@@ -62,10 +70,7 @@ class EvalModel(nn.Module):
         if bg is None:
             return None
         if isinstance(bg, tuple):
-            c = tuple(int(x) for x in bg)
-            if len(c) != 3 or not all(0 <= x <= 255 for x in c):
-                raise ValueError("otvm_amd: a background colour is three values in 0..255, got %r" % (bg,))
-            return c
+            return background_colour(bg)
         t = bg if torch.is_tensor(bg) else torch.from_numpy(np.ascontiguousarray(bg))
         if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[-1] != 3:
             raise ValueError("otvm_amd: a background image is uint8 [H,W,3], got %s %s" % (t.dtype, tuple(t.shape)))

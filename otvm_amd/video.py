@@ -9,6 +9,8 @@ import contextlib
 import numpy as np
 import torch
 
+from . import guided
+from .alpha_model import background_colour
 from .masks import Mask, as_mask
 
 
@@ -127,6 +129,265 @@ def _foreground_option(core, on):
         core.foreground, core._background = saved
 
 
+class _ClipPlan:
+    """What run_video_matte does with a clip, decided before anything is uploaded (host only): every up-front refusal, in the order
+    they have always been made, and the three routes as ONE description, so that the frame loop asks no "which route" question.
+      steps      : (t, kind, first_frame, last_frame, memorize or None = memory_schedule's) in the order they are issued
+      sources    : {frame: one-hot trimap | label map | Mask} of the trimap flow -- ``trimap`` is {0: trimap}, ``mask`` a Mask at
+                   frame 0, ``masks`` a Mask on every frame -- or None: the alphas flow (a trimap derived from each frame's alpha)
+      per_frame  : ``masks``: each source is made into a trimap at its own step and not kept; otherwise upload() makes them all,
+                   once per clip
+      keyed      : the caller gave ``keyframes``: the result carries anchor_frames and schedule
+      natural    : the steps run in frame order (the metrics are fed as the frames come)
+    The model is only asked for the band of a Mask that names none."""
+
+    def __init__(self, model, frames, trimap, alphas, keyframes, mask, masks, backgrounds, work_scale, work_radius, work_eps, skip,
+                 max_num):
+        if work_scale is not None:
+            if work_scale not in guided.SCALES:
+                raise ValueError("run_video_matte: work_scale is 2, 3 or 4 (an integer scale), got %r" % (work_scale,))
+            if work_radius not in guided.RADII:
+                raise ValueError("run_video_matte: work_radius is 1 ... 4, got %r" % (work_radius,))
+            if not work_eps > 0:
+                raise ValueError("run_video_matte: work_eps must be positive, got %r" % (work_eps,))
+            if alphas is not None:
+                raise ValueError("run_video_matte: work_scale belongs to the trimap flow; the alphas flow (VideoMatting108: trimaps "
+                                 "from ground-truth alpha) has no working-resolution route")
+            if backgrounds is not None:
+                raise ValueError("run_video_matte: work_scale takes no per-frame `backgrounds` (they belong to the alphas flow)")
+        T = len(frames)
+        if masks is not None:
+            for name, other in (("trimap", trimap), ("mask", mask), ("keyframes", keyframes), ("alphas", alphas)):
+                if other is not None:
+                    raise ValueError("run_video_matte: `masks` mattes every frame from its own mask and excludes `%s`" % name)
+            masks = [as_mask(m, "run_video_matte: masks[%d]" % j) for j, m in enumerate(masks)]
+            if len(masks) != T:
+                raise ValueError("run_video_matte: `masks` needs one mask per frame, got %d for %d frames" % (len(masks), T))
+            if any(m.role != "key" for m in masks):
+                raise ValueError("run_video_matte: a Mask of `masks` has role 'key' (role='labels' corrects a PROPAGATED trimap; "
+                                 "nothing is propagated here)")
+            for m in masks:
+                m.band_for(model)                         # (a missing band is refused before any frame runs)
+        if mask is not None:
+            if trimap is not None:
+                raise ValueError("run_video_matte: frame 0 has both `trimap` and `mask`")
+            if alphas is not None:
+                raise ValueError("run_video_matte: `mask` belongs to the trimap flow (no per-frame alphas)")
+            if keyframes is not None and 0 in {int(t) for t in keyframes}:
+                raise ValueError("run_video_matte: frame 0 has both `mask` and an entry of `keyframes`")
+            trimap = as_mask(mask, "run_video_matte: mask")
+            if trimap.role != "key":
+                raise ValueError("run_video_matte: `mask` is the first frame's trimap: a Mask with role 'key' (role='labels' "
+                                 "corrects a propagated trimap on a later frame)")
+        # (a plain sequence is checked before anything is uploaded; a streaming source is checked frame by frame in the loop)
+        if (work_scale is not None and T > 0 and (isinstance(frames, (list, tuple, np.ndarray)) or torch.is_tensor(frames))
+                and _as_tensor(frames[0]).dtype != torch.uint8):
+            raise ValueError("run_video_matte: work_scale takes uint8 [H,W,3] frames (float frames have no working-resolution "
+                             "route), got %s" % _as_tensor(frames[0]).dtype)
+        self.keyed = keyframes is not None
+        if keyframes is not None:
+            if alphas is not None:
+                raise ValueError("run_video_matte: keyframes belong to the trimap flow (no per-frame alphas)")
+            keyframes = {int(t): v for t, v in keyframes.items()}
+            if trimap is not None:
+                if 0 in keyframes:
+                    raise ValueError("run_video_matte: frame 0 has both `trimap` and an entry of `keyframes`")
+                keyframes[0] = trimap
+        elif trimap is not None:
+            keyframes = {0: trimap}
+        self.model, self.alphas, self.work_scale = model, alphas, work_scale
+        self.per_frame = masks is not None
+        self.sources = dict(enumerate(masks)) if self.per_frame else keyframes
+        # every launch-stream write the preprocess reads is made once per clip (no per-frame alpha, no per-frame trimap)
+        self.constant_inputs = keyframes is not None
+        self.steps, self.kinds, self.k0, self.natural = [], {}, 0, True
+        self.tri, self.lab, self.ones = {}, {}, None
+        self.mask_hw = {}                                 # frame -> the size of the mask it was given (checked against the frame)
+        if T == 0:
+            return
+        for t, v in (self.sources or {}).items():
+            if isinstance(v, Mask):
+                self.mask_hw[t] = v.shape
+                if not self.per_frame:
+                    v.band_for(model)                     # (as above: a missing band is refused before anything is uploaded)
+        if self.per_frame:
+            self.steps = [(i, "key", True, True, False) for i in range(T)]          # T clips of one frame: nothing to memorise
+        elif keyframes is not None:
+            self.kinds = {t: _keyframe_kind(v) for t, v in keyframes.items()}
+            if "key" not in self.kinds.values():
+                raise ValueError("run_video_matte: keyframes need at least one full trimap (one-hot [3,H,W])")
+            self.k0 = min(t for t, k in self.kinds.items() if k == "key")
+            # the schedule takes the effective skip: the large-input rule needs the resolution the model runs at, which the
+            # trimaps carry
+            h, w = np.shape(keyframes[self.k0])[-2:]
+            if work_scale is not None:
+                h, w = guided.work_size(h, w, work_scale)
+            large = memory_schedule(0, h, w, skip, max_num)[2]
+            self.steps = keyframe_schedule(T, self.kinds, int(skip * 2) if large else skip)
+        else:
+            self.steps = [(i, "frame", i == 0, i == T - 1, None) for i in range(T)]  # alpha flow: eval.py's loop as it is
+        self.natural = all(st[0] == j for j, st in enumerate(self.steps))
+
+    def _trimap(self, v, dev):
+        """One source of kind "key" as the model takes it: [1,1,3,h,w] on the device, reduced to the working resolution."""
+        if isinstance(v, Mask):
+            v = v.convert(self.model, dev)
+        t = _as_tensor(v).to(dev).float()
+        if self.work_scale is not None:
+            t = guided.downsample_trimap(t, self.work_scale)
+        return t[None, None]
+
+    def upload(self, dev):
+        """The part that needs the device, once per clip at the resolution given: the user trimap (25 MB as fp32 at 1080p) is
+        uploaded once, not once per frame.  (``masks`` converts per frame: inputs().)"""
+        if self.per_frame or self.sources is None or not self.steps:
+            return
+        # masks become ordinary trimaps / label maps here, all of them before anything is reduced
+        plain = {t: v.convert(self.model, dev) if isinstance(v, Mask) else v for t, v in self.sources.items()}
+        for t, v in plain.items():
+            if self.kinds[t] == "key":
+                self.tri[t] = self._trimap(v, dev)
+            else:
+                self.lab[t] = _as_tensor(v).to(dev)
+                if self.work_scale is not None:
+                    self.lab[t] = guided.downsample_labels(self.lab[t], self.work_scale)
+
+    def check_masks(self, i, full_hw):
+        """The one refusal of the masks that needs a frame: masks of a keyframe clip are all held against the first frame that
+        comes by, those of ``masks`` each against its own."""
+        for t in ([i] if self.per_frame else list(self.mask_hw)):
+            hw = self.mask_hw.pop(t)
+            if tuple(hw) != tuple(full_hw):
+                raise ValueError("run_video_matte: the mask of frame %d is %dx%d, the frames are %dx%d (masks are given at "
+                                 "the frames' resolution)" % (t, hw[0], hw[1], full_hw[0], full_hw[1]))
+
+    def inputs(self, i, kind, first_frame, H, W, dev):
+        """(a, tri_gt, further keywords) of the model call of step ``i`` at H x W."""
+        if self.sources is None:
+            return _as_tensor(self.alphas[i]).to(dev).float()[None, None, None], None, {}
+        self.ones = _ones_alpha(self.ones, H, W, dev)
+        if self.per_frame:
+            return self.ones, self._trimap(self.sources[i], dev), {}     # this frame's own trimap; nothing is kept of it
+        more = {}
+        if kind == "key" and not first_frame:
+            more["keyframe"] = True
+        elif kind == "labels":
+            more["labels"] = self.lab[i]
+        # (as eval.py does, every frame is handed a trimap -- it comes back as out[2]; only a keyframe consumes it)
+        return self.ones, self.tri.get(i, self.tri[self.k0]), more
+
+
+def _ones_alpha(held, H, W, dev):
+    """The dummy alpha of the trimap flow: one tensor for the whole clip, made anew only when the size changes."""
+    if held is None or held.shape[-2:] != (H, W):
+        held = torch.ones(1, 1, 1, H, W, device=dev)
+    return held
+
+
+def _stage_frame(f, b, dev, frames_are_rgb):
+    """Frame tensor ``f`` and its optional background ``b`` as the model takes them: (fg, bg, H, W, whether the model's
+    ``_frames_rgb`` applies, f's upload event, b's upload event).  The events are those the IO pipeline's prefetcher hangs on what
+    it uploads (``_otvm_ready``); NOTHING waits for them here -- when the launch stream does is the caller's decision."""
+    if f.dtype == torch.uint8 and (b is None or b.dtype == torch.uint8):
+        # decoded images go to the device as they are ([H,W,3] uint8): the preprocess kernel converts, flips the
+        # channel order and composites -- no per-frame torch conversion / transposition kernels
+        fg = f.to(dev, non_blocking=True)
+        bg = fg if b is None else b.to(dev, non_blocking=True)
+        return fg, bg, fg.shape[0], fg.shape[1], True, getattr(f, "_otvm_ready", None), getattr(b, "_otvm_ready", None)
+    planar = []
+    for x in (f, b):                                      # backgrounds come in the same channel order as the frames
+        if x is not None:
+            x = x.to(dev).float()
+            if frames_are_rgb:
+                x = x.flip(-1)
+            x = x.permute(2, 0, 1)[None, None].contiguous()
+        planar.append(x)
+    fg, bg = planar[0], planar[0] if b is None else planar[1]
+    return fg, bg, fg.shape[-2], fg.shape[-1], False, None, None
+
+
+class _WorkingResolution:
+    """``work_scale``'s side of a frame step: stage() reduces the frame for the network, finish() brings alpha (and F) back to
+    H x W through the guided filter and makes the foreground bytes there."""
+
+    def __init__(self, scale, radius, eps, foreground, frames_are_rgb, new_background):
+        self.scale, self.radius, self.eps, self.foreground, self.rgb = scale, radius, eps, foreground, frames_are_rgb
+        self.new_background, self.bg_cache = new_background, {}
+        self.ups, self.full = None, None
+
+    @property
+    def size(self):
+        return None if self.ups is None else (self.ups.h, self.ups.w)
+
+    def stage(self, f, dev):
+        """_stage_frame's tuple for the reduced frame.  Its upload event is waited for HERE: the reduction reads the upload on
+        the launch stream, so no event is left for the caller."""
+        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != 3:
+            raise ValueError("run_video_matte: work_scale takes uint8 [H,W,3] frames (float frames have no "
+                             "working-resolution route), got %s %s" % (f.dtype, tuple(f.shape)))
+        ready = getattr(f, "_otvm_ready", None)
+        self.full = f.to(dev, non_blocking=True).contiguous()
+        if ready is not None:
+            torch.cuda.current_stream(dev).wait_event(ready)
+        if self.ups is None or (self.ups.H, self.ups.W) != tuple(self.full.shape[:2]):
+            self.ups = guided.GuidedUpsampler(dev, self.full.shape[0], self.full.shape[1], self.scale, self.radius, self.eps,
+                                              4 if self.foreground else 1)
+        fg = self.ups.reduce(self.full)
+        return fg, fg, self.ups.h, self.ups.w, True, None, None
+
+    def finish(self, i, fg, alpha, engine, dev):
+        """(alpha, alpha_u8, rgba, comp) at H x W: guided upsampling on this stream, behind the frame; the guide is the working
+        frame the network saw.  The composite is made here, at full resolution, not by the engine."""
+        alpha, u8, fgr_full = self.ups.upsample(self.full, fg, [alpha] + (list(engine.last_fgr) if self.foreground else []))
+        if not self.foreground:
+            return alpha, u8, None, None
+        nb = None if self.new_background is None else _background_at(self.new_background, i, dev, self.bg_cache)
+        if isinstance(nb, tuple):
+            background_colour(nb, "run_video_matte")
+        return (alpha, u8) + self.ups.foreground_bytes(alpha, fgr_full, self.rgb, nb)
+
+
+class _Collector:
+    """The outputs of one clip, placed by frame index (the steps may come in any order) and stacked at the end.  Everything is
+    kept where it is with ``keep_on_device`` and brought to the host as it comes otherwise.  With ``on_foreground`` the foreground
+    frames are handed over and none is kept."""
+
+    def __init__(self, T, keep_on_device, foreground, composite, on_foreground=None):
+        self.keep = (lambda x: x) if keep_on_device else (lambda x: x.cpu())
+        self.alpha, self.u8, self.trimap, self.bank, self.anchors = ([None] * T for _ in range(5))
+        self.on_foreground = on_foreground if foreground else None
+        self.rgba = [None] * T if foreground and on_foreground is None else None
+        self.comp = [None] * T if self.rgba is not None and composite else None
+
+    def log_bank(self, i, frames, anchors=()):
+        """The frame ids resident after frame ``i``'s update, and those of them that are anchors (host lists)."""
+        self.bank[i], self.anchors[i] = list(frames), list(anchors)
+
+    def put(self, i, alpha, u8, trimap, rgba=None, comp=None):
+        self.alpha[i], self.u8[i], self.trimap[i] = self.keep(alpha), self.keep(u8), self.keep(trimap)
+        if self.on_foreground is not None:
+            self.on_foreground(i, rgba, comp)
+        if self.rgba is not None:
+            self.rgba[i] = self.keep(rgba)
+        if self.comp is not None:
+            self.comp[i] = self.keep(comp)
+
+    def result(self, metrics=None, schedule=None, work_size=None):
+        res = dict(alpha=torch.stack(self.alpha), alpha_u8=torch.stack(self.u8), trimap=torch.stack(self.trimap),
+                   bank_frames=self.bank)
+        if schedule is not None:
+            res.update(anchor_frames=self.anchors, schedule=schedule)
+        if work_size is not None:
+            res["work_size"] = work_size
+        if self.rgba is not None:
+            res["fgr_u8"] = torch.stack(self.rgba)
+        if self.comp is not None:
+            res["comp_u8"] = torch.stack(self.comp)
+        if metrics is not None:
+            res["metrics"] = metrics.result()
+        return res
+
+
 def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, skip=10, max_num=5,
                     frames_are_rgb=False, on_frame=None, device=None, keep_on_device=False, gt_alpha_u8=None,
                     gt_mask_u8=None, gt_mask=None, gt_image_metrics=False, gt_flow_metrics=False, foreground=False,
@@ -185,243 +446,69 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
     bank_frames=[per frame: ids of the frames resident in the memory bank after that frame's update]) and, when ``keyframes``
     was given, anchor_frames=[per frame: those of them that are anchors], schedule=[the steps issued, keyframe_schedule's tuples].
     """
-    if work_scale is not None:
-        from . import guided
-        if work_scale not in guided.SCALES:
-            raise ValueError("run_video_matte: work_scale is 2, 3 or 4 (an integer scale), got %r" % (work_scale,))
-        if work_radius not in guided.RADII:
-            raise ValueError("run_video_matte: work_radius is 1 ... 4, got %r" % (work_radius,))
-        if not work_eps > 0:
-            raise ValueError("run_video_matte: work_eps must be positive, got %r" % (work_eps,))
-        if alphas is not None:
-            raise ValueError("run_video_matte: work_scale belongs to the trimap flow; the alphas flow (VideoMatting108: trimaps "
-                             "from ground-truth alpha) has no working-resolution route")
-        if backgrounds is not None:
-            raise ValueError("run_video_matte: work_scale takes no per-frame `backgrounds` (they belong to the alphas flow)")
     frames = list(frames) if not (hasattr(frames, "shape") or hasattr(frames, "__getitem__")) else frames
     T = len(frames)
     dev = device or next(model.parameters()).device
-    mask_hw = {}                                      # frame -> the size of the mask it was given (checked against the frame)
-    if mask is not None or masks is not None:
-        if masks is not None:
-            for name, other in (("trimap", trimap), ("mask", mask), ("keyframes", keyframes), ("alphas", alphas)):
-                if other is not None:
-                    raise ValueError("run_video_matte: `masks` mattes every frame from its own mask and excludes `%s`" % name)
-            masks = [as_mask(m, "run_video_matte: masks[%d]" % j) for j, m in enumerate(masks)]
-            if len(masks) != T:
-                raise ValueError("run_video_matte: `masks` needs one mask per frame, got %d for %d frames" % (len(masks), T))
-            if any(m.role != "key" for m in masks):
-                raise ValueError("run_video_matte: a Mask of `masks` has role 'key' (role='labels' corrects a PROPAGATED trimap; "
-                                 "nothing is propagated here)")
-            for m in masks:
-                m.band_for(model)                         # (a missing band is refused before any frame runs)
-        if mask is not None:
-            if trimap is not None:
-                raise ValueError("run_video_matte: frame 0 has both `trimap` and `mask`")
-            if alphas is not None:
-                raise ValueError("run_video_matte: `mask` belongs to the trimap flow (no per-frame alphas)")
-            if keyframes is not None and 0 in {int(t) for t in keyframes}:
-                raise ValueError("run_video_matte: frame 0 has both `mask` and an entry of `keyframes`")
-            trimap = as_mask(mask, "run_video_matte: mask")
-            if trimap.role != "key":
-                raise ValueError("run_video_matte: `mask` is the first frame's trimap: a Mask with role 'key' (role='labels' "
-                                 "corrects a propagated trimap on a later frame)")
-    ups, work_hw = None, None
-    # (a plain sequence is checked before anything is uploaded; a streaming source is checked frame by frame below)
-    if (work_scale is not None and T > 0 and (isinstance(frames, (list, tuple, np.ndarray)) or torch.is_tensor(frames))
-            and _as_tensor(frames[0]).dtype != torch.uint8):
-        raise ValueError("run_video_matte: work_scale takes uint8 [H,W,3] frames (float frames have no working-resolution "
-                         "route), got %s" % _as_tensor(frames[0]).dtype)
-    out_a, out_u8, out_t, bank_log, anchor_log = [None] * T, [None] * T, [None] * T, [None] * T, [None] * T
-    out_f, out_c, bg_cache = [None] * T, [None] * T, {}
+    plan = _ClipPlan(model, frames, trimap, alphas, keyframes, mask, masks, backgrounds, work_scale, work_radius, work_eps, skip,
+                     max_num)
     core = model.module if hasattr(model, "module") else model
     foreground = bool(foreground) or new_background is not None
+    work = (None if work_scale is None else
+            _WorkingResolution(work_scale, work_radius, work_eps, foreground, frames_are_rgb, new_background))
+    col = _Collector(T, keep_on_device, foreground, new_background is not None, on_foreground)
     metrics = (ClipMetrics(dev, image_metrics=gt_image_metrics, flow_metrics=gt_flow_metrics) if gt_alpha_u8 is not None
                else None)
-    # loop invariants: the user trimap (25 MB as fp32 at 1080p) is uploaded once, not once per frame; the dummy alpha
-    # of the trimap flow is one tensor for the whole clip
-    keyed = keyframes is not None                     # the caller asked for keyframes: the result carries the extra keys
-    if keyframes is not None:
-        if alphas is not None:
-            raise ValueError("run_video_matte: keyframes belong to the trimap flow (no per-frame alphas)")
-        keyframes = {int(t): v for t, v in keyframes.items()}
-        if trimap is not None:
-            if 0 in keyframes:
-                raise ValueError("run_video_matte: frame 0 has both `trimap` and an entry of `keyframes`")
-            keyframes[0] = trimap
-    elif trimap is not None:
-        keyframes = {0: trimap}
-    if keyframes is not None and T > 0:
-        # masks become ordinary trimaps / label maps here, once per clip, at the resolution they were given
-        for t, v in list(keyframes.items()):
-            if isinstance(v, Mask):
-                mask_hw[t] = v.shape
-                keyframes[t] = v.convert(model, dev)
-    tri_devs, lab_devs, steps, k0 = {}, {}, None, 0
-    if keyframes is not None and T > 0:
-        for t, v in keyframes.items():
-            if _keyframe_kind(v) == "key":
-                tri_devs[t] = _as_tensor(v).to(dev).float()
-                if work_scale is not None:
-                    tri_devs[t] = guided.downsample_trimap(tri_devs[t], work_scale)
-                tri_devs[t] = tri_devs[t][None, None]
-            else:
-                lab_devs[t] = _as_tensor(v).to(dev)
-                if work_scale is not None:
-                    lab_devs[t] = guided.downsample_labels(lab_devs[t], work_scale)
-        if not tri_devs:
-            raise ValueError("run_video_matte: keyframes need at least one full trimap (one-hot [3,H,W])")
-        k0 = min(tri_devs)
-        # the schedule takes the effective skip: the large-input rule needs the resolution, which the trimaps carry
-        large = memory_schedule(0, tri_devs[k0].shape[-2], tri_devs[k0].shape[-1], skip, max_num)[2]
-        steps = keyframe_schedule(T, {t: "key" for t in tri_devs} | {t: "labels" for t in lab_devs},
-                                  int(skip * 2) if large else skip)
-    elif masks is not None and T > 0:
-        steps = [(i, "key", True, True, False) for i in range(T)]                   # T clips of one frame: nothing to memorise
-        mask_hw = {i: m.shape for i, m in enumerate(masks)}
-    elif T > 0:
-        steps = [(i, "frame", i == 0, i == T - 1, None) for i in range(T)]          # alpha flow: eval.py's loop as it is
-    natural = steps is None or all(st[0] == j for j, st in enumerate(steps))
-    ones = None
+    plan.upload(dev)
+    bg_cache = {}
     with _foreground_option(core, foreground):
-        for i, kind, first_frame, last_frame, step_memorize in (steps or []):
+        for i, kind, first_frame, last_frame, step_memorize in plan.steps:
             f = _as_tensor(frames[i])
             b = _as_tensor(backgrounds[i]) if backgrounds is not None else None
-            extra = {}
-            if work_scale is not None:
-                if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != 3:
-                    raise ValueError("run_video_matte: work_scale takes uint8 [H,W,3] frames (float frames have no "
-                                     "working-resolution route), got %s %s" % (f.dtype, tuple(f.shape)))
-                ready = getattr(f, "_otvm_ready", None)
-                full = f.to(dev, non_blocking=True).contiguous()
-                if ready is not None:
-                    torch.cuda.current_stream(dev).wait_event(ready)     # the reduction below reads the upload on this stream
-                if ups is None or (ups.H, ups.W) != tuple(full.shape[:2]):
-                    ups = guided.GuidedUpsampler(dev, full.shape[0], full.shape[1], work_scale, work_radius, work_eps,
-                                                 4 if foreground else 1)
-                    work_hw = (ups.h, ups.w)
-                fg = bg = ups.reduce(full)
-                H, W = work_hw
-                full_hw = tuple(full.shape[:2])
-                extra["_frames_rgb"] = bool(frames_are_rgb)
-            elif f.dtype == torch.uint8 and (b is None or b.dtype == torch.uint8):
-                # decoded images go to the device as they are ([H,W,3] uint8): the preprocess kernel converts, flips the
-                # channel order and composites -- no per-frame torch conversion / transposition kernels
-                ready = getattr(f, "_otvm_ready", None)           # upload event of the IO pipeline's prefetcher
-                fg = f.to(dev, non_blocking=True)
-                bg = fg if b is None else b.to(dev, non_blocking=True)
-                if b is not None and getattr(b, "_otvm_ready", None) is not None:
-                    torch.cuda.current_stream(dev).wait_event(b._otvm_ready)
-                H, W = fg.shape[:2]
-                full_hw = (H, W)
-                extra["_frames_rgb"] = bool(frames_are_rgb)
-                if ready is not None:
-                    # the upload event may only travel to the model (whose query-encoder stream then starts on it, ahead of the
-                    # launch stream) when EVERYTHING the preprocess reads is covered by it or loop-invariant: the frame itself
-                    # (no copy made here), no separately uploaded background, and the trimap flow's constant alpha -- a per-frame
-                    # alpha is written by the launch stream just below.  Otherwise the launch stream waits for the upload
-                    # and the model orders its side streams behind the launch stream (ADVICE r2).
-                    if b is None and fg is f and keyframes is not None:
-                        extra["_inputs_ready"] = ready
-                    else:
-                        torch.cuda.current_stream(dev).wait_event(ready)
-            else:
-                f = f.to(dev).float()
-                if frames_are_rgb:
-                    f = f.flip(-1)
-                fg = f.permute(2, 0, 1)[None, None].contiguous()
-                H, W = fg.shape[-2:]
-                if b is not None:                                 # backgrounds come in the same channel order as the frames
-                    b = b.to(dev).float()
-                    if frames_are_rgb:
-                        b = b.flip(-1)
-                    bg = b.permute(2, 0, 1)[None, None].contiguous()
+            fg, bg, H, W, rgb_applies, ready, ready_b = (work.stage(f, dev) if work is not None else
+                                                         _stage_frame(f, b, dev, frames_are_rgb))
+            extra = {"_frames_rgb": bool(frames_are_rgb)} if rgb_applies else {}
+            if ready_b is not None:
+                torch.cuda.current_stream(dev).wait_event(ready_b)
+            if ready is not None:
+                # the upload event may only travel to the model (whose query-encoder stream then starts on it, ahead of the
+                # launch stream) when EVERYTHING the preprocess reads is covered by it or loop-invariant: the frame itself
+                # (no copy made here), no separately uploaded background, and the trimap flow's constant alpha -- a per-frame
+                # alpha or trimap is written by the launch stream just below.  Otherwise the launch stream waits for the upload
+                # and the model orders its side streams behind the launch stream (ADVICE r2).
+                if b is None and fg is f and plan.constant_inputs:
+                    extra["_inputs_ready"] = ready
                 else:
-                    bg = fg
-                full_hw = (H, W)
-            # masks of a keyframe clip are all held against the first frame that comes by, those of `masks` each against its own
-            for t in ([i] if masks is not None else list(mask_hw)):
-                hw = mask_hw.pop(t)
-                if tuple(hw) != tuple(full_hw):
-                    raise ValueError("run_video_matte: the mask of frame %d is %dx%d, the frames are %dx%d (masks are given at "
-                                     "the frames' resolution)" % (t, hw[0], hw[1], full_hw[0], full_hw[1]))
-            if masks is not None:
-                if ones is None or ones.shape[-2:] != (H, W):
-                    ones = torch.ones(1, 1, 1, H, W, device=dev)
-                tri_gt = masks[i].convert(model, dev)             # this frame's own trimap; nothing is kept of it
-                if work_scale is not None:
-                    tri_gt = guided.downsample_trimap(tri_gt, work_scale)
-                a, tri_gt = ones, tri_gt[None, None]
-            elif keyframes is not None:
-                if ones is None or ones.shape[-2:] != (H, W):
-                    ones = torch.ones(1, 1, 1, H, W, device=dev)
-                # (as eval.py does, every frame is handed a trimap -- it comes back as out[2]; only a keyframe consumes it)
-                a, tri_gt = ones, tri_devs.get(i, tri_devs[k0])
-                if kind == "key" and not first_frame:
-                    extra["keyframe"] = True
-                elif kind == "labels":
-                    extra["labels"] = lab_devs[i]
-                if i == k0 - 1:
-                    core.drop_non_anchors()                       # the backward sweep starts from the keyframes alone
-            else:
-                al = alphas[i]
-                al = _as_tensor(al)
-                a = al.to(dev).float()[None, None, None]
-                tri_gt = None
+                    torch.cuda.current_stream(dev).wait_event(ready)
+            plan.check_masks(i, (H, W) if work is None else work.full.shape[:2])
+            a, tri_gt, more = plan.inputs(i, kind, first_frame, H, W, dev)
+            if i == plan.k0 - 1:
+                core.drop_non_anchors()                           # the backward sweep starts from the keyframes alone
             memorize, max_memory_num, large = memory_schedule(i, H, W, skip, max_num)
             if step_memorize is not None:
                 memorize = step_memorize
             if foreground:
-                # (working resolution: the composite is made at full resolution below, not by the engine)
-                core.set_background(None if new_background is None or ups is not None
+                # (working resolution: the composite is made at full resolution by work.finish, not by the engine)
+                core.set_background(None if new_background is None or work is not None
                                     else _background_at(new_background, i, dev, bg_cache))
             out = model(a, fg, bg, tri=None, tri_gt=tri_gt, first_frame=first_frame, last_frame=last_frame,
-                        memorize=memorize, max_memory_num=max_memory_num, large_input=large, _frame_id=i, **extra)
-            alpha = out[3][0, 0, 0]
-            u8 = core._engine.last_alpha_u8
-            rgba = comp = None
-            if ups is not None:
-                # guided upsampling on this stream, behind the frame: the guide is the working frame the network saw
-                alpha, u8, fgr_full = ups.upsample(full, fg, [alpha] + (list(core._engine.last_fgr) if foreground else []))
-                if foreground:
-                    nb = None if new_background is None else _background_at(new_background, i, dev, bg_cache)
-                    if isinstance(nb, tuple) and not (len(nb) == 3 and all(0 <= int(x) <= 255 for x in nb)):
-                        raise ValueError("run_video_matte: a background colour is three values in 0..255, got %r" % (nb,))
-                    rgba, comp = ups.foreground_bytes(alpha, fgr_full, frames_are_rgb, nb)
+                        memorize=memorize, max_memory_num=max_memory_num, large_input=large, _frame_id=i, **extra, **more)
+            alpha, u8, rgba, comp = out[3][0, 0, 0], core._engine.last_alpha_u8, None, None
+            if work is not None:
+                alpha, u8, rgba, comp = work.finish(i, fg, alpha, core._engine, dev)
             elif foreground:
                 rgba, comp = core._engine.last_rgba_u8, core._engine.last_comp_u8
-            mem_now = core.memories                                 # frame ids resident after this frame's update (host lists)
-            bank_log[i], anchor_log[i] = list(mem_now["frames"]), list(mem_now["anchors"])
-            if metrics is not None and natural:
+            mem_now = core.memories
+            col.log_bank(i, mem_now["frames"], mem_now["anchors"])
+            if metrics is not None and plan.natural:
                 _metrics_add(metrics, u8, i, gt_alpha_u8, gt_mask_u8, gt_mask, dev)
             if on_frame is not None:
                 on_frame(i, alpha, u8, out)
-            if keep_on_device:
-                out_a[i], out_u8[i], out_t[i] = alpha, u8, out[1][0, 0]
-            else:
-                out_a[i], out_u8[i], out_t[i] = alpha.cpu(), u8.cpu(), out[1][0, 0].cpu()
-            if foreground and on_foreground is not None:
-                on_foreground(i, rgba, comp)
-            elif foreground:
-                out_f[i] = rgba if keep_on_device else rgba.cpu()
-                if new_background is not None:
-                    out_c[i] = comp if keep_on_device else comp.cpu()
-    if metrics is not None and not natural:
+            col.put(i, alpha, u8, out[1][0, 0], rgba, comp)
+    if metrics is not None and not plan.natural:
         # the pair terms (dtSSD, MESSDdt) depend on the order: fed in natural frame order from the kept 8-bit alphas
         for i in range(T):
-            _metrics_add(metrics, out_u8[i].to(dev), i, gt_alpha_u8, gt_mask_u8, gt_mask, dev)
-    res = dict(alpha=torch.stack(out_a), alpha_u8=torch.stack(out_u8), trimap=torch.stack(out_t), bank_frames=bank_log)
-    if keyed:
-        res.update(anchor_frames=anchor_log, schedule=list(steps or []))
-    if work_scale is not None:
-        res["work_size"] = work_hw
-    if foreground and on_foreground is None:
-        res["fgr_u8"] = torch.stack(out_f)
-        if new_background is not None:
-            res["comp_u8"] = torch.stack(out_c)
-    if metrics is not None:
-        res["metrics"] = metrics.result()
-    return res
+            _metrics_add(metrics, col.u8[i].to(dev), i, gt_alpha_u8, gt_mask_u8, gt_mask, dev)
+    return col.result(metrics, list(plan.steps) if plan.keyed else None, None if work is None else work.size)
 
 
 def _metrics_add(metrics, u8, i, gt_alpha_u8, gt_mask_u8, gt_mask, dev):
@@ -468,14 +555,14 @@ def run_video_matte_batch(model, clips, trimaps=None, alphas=None, backgrounds=N
         raise ValueError("run_video_matte_batch: give either trimaps (demo flow) or alphas (VideoMatting108 flow)")
     core = model.module if hasattr(model, "module") else model
     dev = device or next(core.parameters()).device
-    res = [dict(alpha=[], alpha_u8=[], trimap=[], bank_frames=[], fgr_u8=[], comp_u8=[]) for _ in range(B)]
     foreground = bool(foreground) or new_background is not None
     if new_background is not None and not (isinstance(new_background, list) and len(new_background) == B):
         raise ValueError("run_video_matte_batch: new_background is a list of one entry per clip")
+    cols = [_Collector(n, keep_on_device, foreground, new_background is not None) for n in lens]
     bg_cache = [{} for _ in range(B)]
     metrics = ([ClipMetrics(dev, image_metrics=gt_image_metrics, flow_metrics=gt_flow_metrics) for _ in range(B)]
-               if gt_alpha_u8 is not None else None)
-    tri_dev = None if trimaps is None else [_as_tensor(t).to(dev).float()[None, None] for t in trimaps]
+               if gt_alpha_u8 is not None else [None] * B)
+    tri_dev = [None] * B if trimaps is None else [_as_tensor(t).to(dev).float()[None, None] for t in trimaps]
     ones = None
     with _foreground_option(core, foreground):
         for i in range(T):
@@ -484,36 +571,15 @@ def run_video_matte_batch(model, clips, trimaps=None, alphas=None, backgrounds=N
                 j = min(i, lens[b] - 1)                               # a clip that has ended repeats its last frame (discarded)
                 f = _as_tensor(clips[b][j])
                 bk = _as_tensor(backgrounds[b][j]) if backgrounds is not None else None
-                if f.dtype == torch.uint8 and (bk is None or bk.dtype == torch.uint8):
-                    fg = f.to(dev, non_blocking=True)
-                    bg = fg if bk is None else bk.to(dev, non_blocking=True)
-                    # frames handed over by the IO pipeline's prefetcher carry their upload event: the launch stream waits for
-                    # it before anything reads them (as run_video_matte does; the batched step makes no promise to the engine
-                    # about its inputs, so its side streams order themselves behind the launch stream)
-                    for src in (f, bk):
-                        ev = getattr(src, "_otvm_ready", None) if src is not None else None
-                        if ev is not None:
-                            torch.cuda.current_stream(dev).wait_event(ev)
-                    H, W = fg.shape[:2]
-                    rgb = bool(frames_are_rgb)
-                else:
-                    f = f.to(dev).float()
-                    if frames_are_rgb:
-                        f = f.flip(-1)
-                    fg = f.permute(2, 0, 1)[None, None].contiguous()
-                    H, W = fg.shape[-2:]
-                    if bk is not None:
-                        bk = bk.to(dev).float()
-                        if frames_are_rgb:
-                            bk = bk.flip(-1)
-                        bg = bk.permute(2, 0, 1)[None, None].contiguous()
-                    else:
-                        bg = fg
-                    rgb = False
+                fg, bg, H, W, rgb_applies, *events = _stage_frame(f, bk, dev, frames_are_rgb)
+                # frames handed over by the IO pipeline's prefetcher carry their upload event: the launch stream waits for
+                # it before anything reads them (the batched step makes no promise to the engine about its inputs, so its
+                # side streams order themselves behind the launch stream)
+                for ev in events:
+                    if ev is not None:
+                        torch.cuda.current_stream(dev).wait_event(ev)
                 if trimaps is not None:
-                    if ones is None or ones.shape[-2:] != (H, W):
-                        ones = torch.ones(1, 1, 1, H, W, device=dev)
-                    a = ones
+                    a = ones = _ones_alpha(ones, H, W, dev)
                 else:
                     a = _as_tensor(alphas[b][j]).to(dev).float()[None, None, None]
                 A.append(a), FG.append(fg), BG.append(bg)
@@ -521,40 +587,22 @@ def run_video_matte_batch(model, clips, trimaps=None, alphas=None, backgrounds=N
             if foreground:
                 core.set_background(None if new_background is None else
                                     [_background_at(new_background[b], min(i, lens[b] - 1), dev, bg_cache[b]) for b in range(B)])
-            outs = core.forward_batch(A, FG, BG, tri_dev if tri_dev is not None else [None] * B, first_frame=(i == 0),
-                                      last_frame=(i == T - 1), memorize=memorize, max_memory_num=max_memory_num, large_input=large,
-                                      _frames_rgb=rgb)
-            u8s = core._engine.last_alpha_u8_b
-            bank = list(core.memories["frames"])
+            outs = core.forward_batch(A, FG, BG, tri_dev, first_frame=(i == 0), last_frame=(i == T - 1), memorize=memorize,
+                                      max_memory_num=max_memory_num, large_input=large,
+                                      _frames_rgb=rgb_applies and bool(frames_are_rgb))
+            eng, bank = core._engine, core.memories["frames"]              # (one look at the bank per step)
             for b in range(B):
                 if i >= lens[b]:
                     continue
-                al, u8, tr = outs[b][3][0, 0, 0], u8s[b], outs[b][1][0, 0]
-                if metrics is not None:
-                    metrics[b].add(u8, _as_tensor(gt_alpha_u8[b][i]).to(dev), gt_mask)
+                u8 = eng.last_alpha_u8_b[b]
+                cols[b].log_bank(i, bank)
+                if metrics[b] is not None:
+                    _metrics_add(metrics[b], u8, i, gt_alpha_u8[b], None, gt_mask, dev)
                 if on_frame is not None:
-                    on_frame(b, i, al, u8, outs[b])
-                if not keep_on_device:
-                    al, u8, tr = al.cpu(), u8.cpu(), tr.cpu()
-                res[b]["alpha"].append(al), res[b]["alpha_u8"].append(u8), res[b]["trimap"].append(tr)
-                res[b]["bank_frames"].append(bank)
-                if foreground:
-                    eng = core._engine
-                    res[b]["fgr_u8"].append(eng.last_rgba_u8_b[b] if keep_on_device else eng.last_rgba_u8_b[b].cpu())
-                    if new_background is not None:
-                        res[b]["comp_u8"].append(eng.last_comp_u8_b[b] if keep_on_device else eng.last_comp_u8_b[b].cpu())
-    out = []
-    for b, r in enumerate(res):
-        d = dict(alpha=torch.stack(r["alpha"]), alpha_u8=torch.stack(r["alpha_u8"]), trimap=torch.stack(r["trimap"]),
-                 bank_frames=r["bank_frames"])
-        if metrics is not None:
-            d["metrics"] = metrics[b].result()
-        if foreground:
-            d["fgr_u8"] = torch.stack(r["fgr_u8"])
-            if new_background is not None:
-                d["comp_u8"] = torch.stack(r["comp_u8"])
-        out.append(d)
-    return out
+                    on_frame(b, i, outs[b][3][0, 0, 0], u8, outs[b])
+                cols[b].put(i, outs[b][3][0, 0, 0], u8, outs[b][1][0, 0], eng.last_rgba_u8_b[b] if foreground else None,
+                            eng.last_comp_u8_b[b] if new_background is not None else None)
+    return [col.result(m) for col, m in zip(cols, metrics)]
 
 
 class ClipMetrics:

@@ -400,6 +400,15 @@ def test_foreground_batched_equals_single(synth_sd, tmp_path, monkeypatch):
             assert torch.equal(batched[b][k], single[b][k]), (b, k)
         for k in ("alpha", "alpha_u8", "trimap"):
             assert torch.equal(off[b][k], single[b][k]), (b, k)
+    # keep_on_device changes where the results live and nothing else: one clip over a colour, and the two-clip batch
+    kept = run_video_matte(m, clips[1][0], trimap=clips[1][1], skip=2, max_num=3, foreground=True, new_background=bgs[1],
+                           keep_on_device=True)
+    kept_b = run_video_matte_batch(m, [c[0] for c in clips], trimaps=[c[1] for c in clips], skip=2, max_num=3, foreground=True,
+                                   new_background=bgs, keep_on_device=True)
+    for on_device, on_host in [(kept, single[1])] + list(zip(kept_b, batched)):
+        for k in ("alpha", "alpha_u8", "trimap", "fgr_u8", "comp_u8"):
+            assert on_device[k].is_cuda and not on_host[k].is_cuda, k
+            assert torch.equal(on_device[k].cpu(), on_host[k]), k
 
 
 def test_recomputed_first_frame_publishes_the_returned_frame(synth_sd, monkeypatch):
