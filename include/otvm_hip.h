@@ -68,7 +68,9 @@ const char* otvm_last_error(void);
                                   likewise otvm_trimap_apply_labels, the label pass of the keyframe corrections;
                                   likewise working-resolution matting: otvm_downsample_u8 / _trimap / _labels, otvm_guided_ws_bytes,
                                   otvm_guided_coeffs and otvm_guided_apply with their struct otvm_guided_params;
-                                  likewise trimaps from masks: otvm_trimap_from_mask / _ws_bytes with otvm_mask_trimap_params) */
+                                  likewise trimaps from masks: otvm_trimap_from_mask / _ws_bytes with otvm_mask_trimap_params;
+                                  likewise the temporal stabilisation of alpha: otvm_luma_u8 and otvm_temporal_blend with
+                                  otvm_temporal_params) */
 int otvm_abi_version(void);
 
 /* ---------------------------------------------------------------- weights (load time) ----------
@@ -611,6 +613,47 @@ int otvm_optflow_farneback_params(int H, int W, int* levels, float* blur_taps, f
  * ws: otvm_optflow_farneback_ws_bytes(H, W).                                                                         */
 int otvm_matting_messddt(const uint8_t* p0, const uint8_t* t0, const uint8_t* m0, const uint8_t* p1, const uint8_t* t1,
                          const uint8_t* m1, int H, int W, double* acc, float* flow_out, void* ws, void* stream);
+
+/* ---------------------------------------------------------------- temporal stabilisation of alpha ----------
+ * A causal, one-frame-state, motion-compensated recursive filter of alpha (an extension; the reference mattes every frame on
+ * its own).  The defaults of otvm_amd/temporal.py are PLACEHOLDERS: there is no trained checkpoint here, the filter is checked
+ * by definition and by property on synthetic clips, not by quality on real footage.  New symbols only (additive, as the
+ * entries above): the ABI number stays.
+ *
+ * otvm_luma_u8: img uint8 [H,W,3] -> grey uint8 [H,W] = (B*1868 + G*9617 + R*4899 + 8192) >> 14 (integer: OpenCV's BGR2GRAY);
+ * u8_rgb says which byte is R, as otvm_preprocess_params.u8_rgb does.  H in 1..65535, W >= 1.
+ *
+ * otvm_temporal_blend, per pixel (x, y), fp32, one IEEE operation per step, no atomics (two calls give equal bits):
+ *   sx = (float)x + dx, sy = (float)y + dy with (dx, dy) = flow[y][x]: the flow from this frame to the previous one
+ *        (otvm_optflow_farneback(prev = grey, next = grey_prev)).  ok = 0 <= sx <= W-1 && 0 <= sy <= H-1 (NaN and inf fail);
+ *        when !ok nothing is gathered and w = 0.
+ *   bilinear sample at (sx, sy): x0 = floorf(sx), fx = sx - x0, x1 = min(x0 + 1, W-1), likewise y;
+ *        top = ((1-fx)*v00) + (fx*v01), bot = ((1-fx)*v10) + (fx*v11), v = ((1-fy)*top) + (fy*bot);
+ *        taken of prev, giving sw, and of (float)grey_prev, giving gw.
+ *   wc = max(0, 1 - |(float)grey - gw| * inv_tau_colour)     the photometric residual, which doubles as the occlusion test
+ *   wa = max(0, 1 - |a - sw| * inv_tau_alpha)                a real change of alpha is not smoothed away
+ *   gate = 1 without tri; otherwise with (t0, t1, t2) = tri[.][min(y / tri_scale, th-1)][min(x / tri_scale, tw-1)]
+ *        gate = (t1 > t0 && t1 >= t2): numpy's first-max argmax equal to 1 (the unknown class), NaN gives 0
+ *   w = ((strength*wc)*wa)*gate;  o = a + (w * (sw - a));  out = min(max(o, 0), 1) (-0.0 and NaN give +0.0);
+ *   out_u8 = (uint8) trunc(out * 255.f), the byte otvm_crop_outputs writes.  A non-finite a gives out = a, byte 0.
+ * prev == NULL is the first frame of a clip: w = 0 everywhere (out = the clamped alpha and its byte); grey, grey_prev, flow
+ * and tri are not read.  (float)x is exact for W <= 2^24.                                                                */
+typedef struct otvm_temporal_params {
+    int H, W;                       /* H in 1..65535, W >= 1 */
+    const float* alpha;             /* [H,W]: this frame's raw alpha */
+    const float* prev;              /* [H,W]: the previous STABILISED alpha, every value in [0,1]; NULL = first frame */
+    const uint8_t* grey;            /* [H,W]: this frame's luma */
+    const uint8_t* grey_prev;       /* [H,W]: the previous frame's luma */
+    const float* flow;              /* [H,W,2] = (dx, dy) */
+    const float* tri;               /* planar [3,th,tw] (bg, unknown, fg) or NULL */
+    int th, tw, tri_scale;
+    float strength;                 /* in [0,1] */
+    float inv_tau_colour, inv_tau_alpha;   /* positive, finite; reciprocals taken on the host in fp32 */
+    float* out;                     /* [H,W]; must not alias prev */
+    uint8_t* out_u8;                /* [H,W] or NULL */
+} otvm_temporal_params;
+int otvm_luma_u8(const uint8_t* img, int H, int W, int u8_rgb, uint8_t* grey, void* stream);
+int otvm_temporal_blend(const otvm_temporal_params* p, void* stream);
 
 /* ---------------------------------------------------------------- range guard / clear -----------
  * f16x3 splits fp32 operands into fp16 halves: |x| >= 65504 loses accuracy, >= 131008 becomes inf.

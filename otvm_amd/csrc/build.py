@@ -32,6 +32,7 @@ SOURCES = [
     ("guided.hip", ["-ffp-contract=off"]),
     ("edt.hip", ["-ffp-contract=off"]),
     ("mask_trimap.hip", ["-ffp-contract=off"]),
+    ("temporal.hip", ["-ffp-contract=off"]),
     ("memory_read.hip", []),
     ("memory_read_f16x3.hip", []),
     ("metrics.hip", []),

@@ -30,6 +30,13 @@ band into the foreground / background in pixels (default: the --trimap dilation)
 >= HI, background <= LO; default 127,128) -- placeholders, not tuned on real footage.  Works with --fgr, --composite, --work-scale
 and, in key mode, --keyframes (labels/ too); refused with --batch > 1 and without --demo.  The summary carries masks, mask_band
 and mask_thresholds.
+--stabilise [K] (demo layout): temporal stabilisation of alpha -- a causal, flow-compensated recursive filter of strength K in
+[0,1] behind every frame (video.run_video_matte(stabilise=...), otvm_amd/temporal.py); --stabilise-taus C,A sets the grey residual
+and the change of alpha at which it lets go, --stabilise-region unknown|all where it acts.  The alpha PNGs, and with --fgr /
+--composite the foreground bytes, carry the stabilised alpha.  The defaults (0.5; 24,0.5) are PLACEHOLDERS: there is no trained
+checkpoint here, the filter is checked by definition and by property on synthetic clips, not by quality on real footage.  Works
+with --masks, --keyframes (forward-only schedules), --work-scale, --fgr and --composite; refused with --viz, --batch > 1 and
+without --demo.  The summary carries stabilise.
 Frame IO runs through otvm_amd/io_pipeline.py: the demo flow decodes ahead in a thread pool and uploads on a copy
 stream, both flows download the 8-bit alphas asynchronously and PNG-encode them in a pool (the reference's loop blocks
 on .cpu() + cv2.imwrite per frame, eval.py:209-217).
@@ -82,6 +89,29 @@ def parse_mask_options(band, thresholds):
     return b, (lo, hi)
 
 
+def parse_stabilise_options(strength, taus, region):
+    """--stabilise [K], --stabilise-taus "C,A", --stabilise-region -> run_video_matte's ``stabilise`` dict (None when --stabilise
+    was not given); checked as temporal.TemporalStabiliser does."""
+    from .temporal import check_options
+    if strength is None:
+        if taus is not None or region is not None:
+            raise SystemExit("eval_cli: --stabilise-taus / --stabilise-region belong to --stabilise")
+        return None
+    kw = {"strength": strength}
+    if taus is not None:
+        try:
+            kw["tau_colour"], kw["tau_alpha"] = (float(x) for x in taus.split(","))
+        except ValueError as e:
+            raise SystemExit("eval_cli: --stabilise-taus is C,A (grey levels, alpha), both positive, got %r (%s)" % (taus, e))
+    if region is not None:
+        kw["region"] = region
+    try:
+        check_options(**kw)
+    except ValueError as e:
+        raise SystemExit("eval_cli: --stabilise K takes a strength in [0,1], --stabilise-taus C,A two positive numbers (%s)" % e)
+    return kw
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--data", required=True)
@@ -105,6 +135,14 @@ def main(argv=None):
                     help="--masks: reach of the unknown band into foreground / background in pixels (default: the --trimap dilation)")
     ap.add_argument("--mask-thresholds", default="127,128", metavar="LO,HI",
                     help="--masks: foreground is mask >= HI, background mask <= LO (8-bit scale)")
+    ap.add_argument("--stabilise", type=float, nargs="?", const=0.5, default=None, metavar="K",
+                    help="demo layout: temporal stabilisation of alpha, a flow-compensated recursive filter of strength K in [0,1] "
+                         "(default 0.5: a placeholder, not tuned on real footage)")
+    ap.add_argument("--stabilise-taus", default=None, metavar="C,A",
+                    help="--stabilise: the grey residual (8-bit levels) and the change of alpha at which the filter lets go "
+                         "(default 24,0.5: placeholders)")
+    ap.add_argument("--stabilise-region", default=None, choices=["unknown", "all"],
+                    help="--stabilise: filter only the trimap's unknown class (default) or every pixel")
     ap.add_argument("--max-frames", type=int, default=None, help="only the first N frames of every sequence")
     ap.add_argument("--weights", default=None)
     ap.add_argument("--synthetic-weights", action="store_true")
@@ -134,6 +172,16 @@ def main(argv=None):
 
     comp_color, comp_image = parse_composite(args.composite)
     mask_band, (mask_lo, mask_hi) = parse_mask_options(args.mask_band, args.mask_thresholds)
+    stabilise = parse_stabilise_options(args.stabilise, args.stabilise_taus, args.stabilise_region)
+    if stabilise is not None and not args.demo:
+        raise SystemExit("eval_cli: --stabilise belongs to the demo routes (the VideoMatting108 flow composites every frame over a "
+                         "background of its own); add --demo")
+    if stabilise is not None and args.batch is not None and args.batch > 1:
+        raise SystemExit("eval_cli: --batch %d steps clips in lock-step through matte_batch, which does not implement --stabilise"
+                         % args.batch)
+    if stabilise is not None and args.viz:
+        raise SystemExit("eval_cli: --stabilise changes alpha behind the frame; the --viz panels show the network's own outputs: "
+                         "drop one of them")
     if args.masks and not args.demo:
         raise SystemExit("eval_cli: --masks reads the demo layout's mask/ folder; add --demo")
     if args.masks and args.batch is not None and args.batch > 1:
@@ -200,7 +248,7 @@ def main(argv=None):
         # (--viz and --sync-io are single-clip features -- matte_batch writes no viz frames and decodes every clip of a group up
         #  front -- so they keep batch 1 unless --batch is given explicitly)
         if world > 1 and any(k is not None for k in keys) and not (args.viz or args.sync_io or args.fgr or args.composite
-                                                                   or args.keyframes or args.masks):
+                                                                   or args.keyframes or args.masks or stabilise is not None):
             def padded(k):
                 lw, uw, lh, uh = pad_amounts(k[0], k[1], 32)
                 return (k[0] + lh + uh) * (k[1] + lw + uw)
@@ -254,6 +302,8 @@ def main(argv=None):
         fwriter = AlphaWriter(dev, os.path.join(args.out, "fgr", seq["name"]), png_names) if args.fgr else None
         cwriter = AlphaWriter(dev, os.path.join(args.out, "comp", seq["name"]), png_names) if args.composite is not None else None
         eng_of = model.module
+        # --work-scale and --stabilise remake the foreground bytes behind the engine: they arrive through on_foreground
+        late_bytes = args.work_scale is not None or stabilise is not None
         bgr = not (demo and not args.sync_io and not keyed)   # the prefetcher hands out RGB frames, the decoded arrays are BGR
 
         def new_background():
@@ -273,15 +323,15 @@ def main(argv=None):
                 Image.fromarray(u8.cpu().numpy()).save(os.path.join(outdir, data["names"][i] + ".png"))
             else:
                 writer.put(i, u8)
-            if fwriter is not None and args.work_scale is None:
+            if fwriter is not None and not late_bytes:
                 fwriter.put(i, eng_of._engine.last_rgba_u8, bgr=bgr)
-            if cwriter is not None and args.work_scale is None:
+            if cwriter is not None and not late_bytes:
                 cwriter.put(i, eng_of._engine.last_comp_u8, bgr=bgr)
             if args.viz:
                 viz.write_viz_frame(os.path.join(vizdir, "f%d.jpg" % i), out)
         def save_full(i, rgba, comp):
             # --work-scale: the engine's foreground bytes are at the working resolution; the full-resolution ones arrive here,
-            # frame by frame, and go to the writers as the others do
+            # frame by frame, and go to the writers as the others do (--stabilise: those of the stabilised alpha)
             if fwriter is not None:
                 fwriter.put(i, rgba, bgr=bgr)
             if cwriter is not None:
@@ -321,8 +371,9 @@ def main(argv=None):
                                   max_num=args.max_num, masks=per_frame,
                                   on_frame=save, device=dev, frames_are_rgb=rgb, keep_on_device=True,
                                   foreground=want_fgr, new_background=new_background(), keyframes=kf,
-                                  **(dict(work_scale=args.work_scale, work_radius=args.work_radius, work_eps=args.work_eps,
-                                          on_foreground=save_full if want_fgr else None)
+                                  stabilise=stabilise,
+                                  **(dict(on_foreground=save_full if want_fgr else None) if late_bytes else {}),
+                                  **(dict(work_scale=args.work_scale, work_radius=args.work_radius, work_eps=args.work_eps)
                                      if args.work_scale is not None else {}))
             if pre is not None:
                 pre.close()
@@ -339,7 +390,7 @@ def main(argv=None):
         for w in (fwriter, cwriter):
             if w is not None:
                 w.close()
-        for k in ("fgr_u8", "comp_u8"):
+        for k in ("fgr_u8", "comp_u8", "alpha_raw"):
             res.pop(k, None)                       # written as PNGs; the per-clip results keep today's keys
         if args.viz:
             viz.make_viz_video(os.path.join(vizdir, "f%d.jpg"),                          # eval.py:229-242
@@ -380,6 +431,9 @@ def main(argv=None):
         summary["masks"] = args.masks
         summary["mask_band"] = list(mask_band) if isinstance(mask_band, tuple) else [dk if mask_band is None else mask_band] * 2
         summary["mask_thresholds"] = [mask_lo, mask_hi]
+    if stabilise is not None:
+        summary["stabilise"] = {k: stabilise.get(k, d) for k, d in (("strength", 0.5), ("tau_colour", 24.0), ("tau_alpha", 0.5),
+                                                                      ("region", "unknown"))}
     if distributed:
         import torch.distributed as dist
         # which kernel configurations this rank launched (fp32 summation orders): identical on all ranks by construction

@@ -52,6 +52,32 @@ def downsample_labels(labels, scale):
     return _reduce(L.load().otvm_downsample_labels, "downsample_labels", labels, torch.uint8, False, scale)
 
 
+def foreground_bytes(alpha, fgr, rgb, background=None, who="otvm_amd.guided"):
+    """RGBA [H,W,4] and, over ``background`` (a colour triple or a uint8 [H,W,3] device tensor), the composite [H,W,3] of an
+    alpha plane [H,W] and the F planes [3,H,W] (fp32, unpadded): otvm_fgr_outputs.  Shared by the guided upsampler and the
+    temporal stabilisation, which both remake the bytes from an alpha the engine did not write."""
+    H, W = alpha.shape[-2:]
+    device = alpha.device
+    q = L.FgrParams()
+    q.alpha_p, q.fgr_p = alpha.data_ptr(), fgr.data_ptr()
+    q.Hp, q.Wp, q.H, q.W, q.lh, q.lw, q.u8_rgb = H, W, H, W, 0, 0, int(bool(rgb))
+    rgba = torch.empty((H, W, 4), dtype=torch.uint8, device=device)
+    q.rgba_u8 = rgba.data_ptr()
+    comp = None
+    if background is not None:
+        comp = torch.empty((H, W, 3), dtype=torch.uint8, device=device)
+        q.comp_u8 = comp.data_ptr()
+        if torch.is_tensor(background):
+            if background.dtype != torch.uint8 or tuple(background.shape) != (H, W, 3) or not background.is_contiguous():
+                raise ValueError("%s: a background image is a contiguous uint8 [%d,%d,3] tensor (got %s %s)"
+                                 % (who, H, W, background.dtype, tuple(background.shape)))
+            q.bg_u8 = background.data_ptr()
+        else:
+            q.bg_color[:] = [int(c) for c in background]
+    L.check(L.load().otvm_fgr_outputs(C.byref(q), _stream(device)), "fgr_outputs")
+    return rgba, comp
+
+
 class GuidedUpsampler:
     """Brings working-resolution targets (alpha, or alpha + the three F planes) back to H x W with the colour-guide fast guided
     filter.  Owns the coefficient buffers of one resolution (allocated once); the outputs are fresh tensors per call."""
@@ -123,21 +149,4 @@ class GuidedUpsampler:
     def foreground_bytes(self, alpha, fgr, rgb, background=None):
         """RGBA [H,W,4] and, over ``background`` (a colour triple or a uint8 [H,W,3] device tensor), the composite [H,W,3]:
         otvm_fgr_outputs on the full-resolution planes (no padding)."""
-        q = L.FgrParams()
-        q.alpha_p, q.fgr_p = alpha.data_ptr(), fgr.data_ptr()
-        q.Hp, q.Wp, q.H, q.W, q.lh, q.lw, q.u8_rgb = self.H, self.W, self.H, self.W, 0, 0, int(bool(rgb))
-        rgba = torch.empty((self.H, self.W, 4), dtype=torch.uint8, device=self.device)
-        q.rgba_u8 = rgba.data_ptr()
-        comp = None
-        if background is not None:
-            comp = torch.empty((self.H, self.W, 3), dtype=torch.uint8, device=self.device)
-            q.comp_u8 = comp.data_ptr()
-            if torch.is_tensor(background):
-                if background.dtype != torch.uint8 or tuple(background.shape) != (self.H, self.W, 3) or not background.is_contiguous():
-                    raise ValueError("GuidedUpsampler: a background image is a contiguous uint8 [%d,%d,3] tensor (got %s %s)"
-                                     % (self.H, self.W, background.dtype, tuple(background.shape)))
-                q.bg_u8 = background.data_ptr()
-            else:
-                q.bg_color[:] = [int(c) for c in background]
-        L.check(self.lib.otvm_fgr_outputs(C.byref(q), _stream(self.device)), "fgr_outputs")
-        return rgba, comp
+        return foreground_bytes(alpha, fgr, rgb, background, "GuidedUpsampler")

@@ -92,6 +92,12 @@ class MaskTrimapParams(C.Structure):
                 ("trimap", vp), ("labels", vp), ("band_label", i32)]
 
 
+class TemporalParams(C.Structure):
+    _fields_ = [("H", i32), ("W", i32), ("alpha", vp), ("prev", vp), ("grey", vp), ("grey_prev", vp), ("flow", vp), ("tri", vp),
+                ("th", i32), ("tw", i32), ("tri_scale", i32), ("strength", f32), ("inv_tau_colour", f32), ("inv_tau_alpha", f32),
+                ("out", vp), ("out_u8", vp)]
+
+
 class PpmHeadParams(C.Structure):
     _fields_ = [("pooled", vp), ("C", i32), ("K_pad", i32), ("Cout", i32),
                 ("w", vp * 4), ("bias", vp * 4), ("gamma", vp * 4), ("beta", vp * 4), ("out", vp * 4),
@@ -165,6 +171,8 @@ _PROTOS = {
     "otvm_optflow_farneback_ws_bytes": (i64, [i32, i32]),
     "otvm_optflow_farneback_params": (i32, [i32, i32, vp, vp, vp, vp, vp]),
     "otvm_matting_messddt": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "otvm_luma_u8": (i32, [vp, i32, i32, i32, vp, vp]),
+    "otvm_temporal_blend": (i32, [C.POINTER(TemporalParams), vp]),
     "otvm_gn_stats_b": (i32, [vp, i64, i32, i32, vp, i32, i64, i32, vp]),
     "otvm_gn_table_b": (i32, [vp, i64, i32, vp, vp, vp, vp, i32, i32, i32, vp]),
     "otvm_gn_apply_b": (i32, [C.POINTER(GnApplyParams), vp]),

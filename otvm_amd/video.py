@@ -9,7 +9,7 @@ import contextlib
 import numpy as np
 import torch
 
-from . import guided
+from . import guided, temporal
 from .alpha_model import background_colour
 from .masks import Mask, as_mask
 
@@ -335,16 +335,57 @@ class _WorkingResolution:
         fg = self.ups.reduce(self.full)
         return fg, fg, self.ups.h, self.ups.w, True, None, None
 
-    def finish(self, i, fg, alpha, engine, dev):
+    def finish(self, i, fg, alpha, engine, dev, make_bytes=True):
         """(alpha, alpha_u8, rgba, comp) at H x W: guided upsampling on this stream, behind the frame; the guide is the working
-        frame the network saw.  The composite is made here, at full resolution, not by the engine."""
-        alpha, u8, fgr_full = self.ups.upsample(self.full, fg, [alpha] + (list(engine.last_fgr) if self.foreground else []))
-        if not self.foreground:
+        frame the network saw.  The composite is made here, at full resolution, not by the engine.  make_bytes=False leaves the
+        foreground bytes to a later foreground_bytes() (the temporal stabilisation changes alpha first)."""
+        alpha, u8, self.fgr_full = self.ups.upsample(self.full, fg, [alpha] + (list(engine.last_fgr) if self.foreground else []))
+        if not (self.foreground and make_bytes):
             return alpha, u8, None, None
+        return (alpha, u8) + self.foreground_bytes(i, alpha, dev)
+
+    def foreground_bytes(self, i, alpha, dev):
+        """(rgba, comp) of ``alpha`` and the frame's full-resolution F over frame ``i``'s new background"""
         nb = None if self.new_background is None else _background_at(self.new_background, i, dev, self.bg_cache)
         if isinstance(nb, tuple):
             background_colour(nb, "run_video_matte")
-        return (alpha, u8) + self.ups.foreground_bytes(alpha, fgr_full, self.rgb, nb)
+        return self.ups.foreground_bytes(alpha, self.fgr_full, self.rgb, nb)
+
+
+class _Stabilisation:
+    """``stabilise``'s side of a frame step: the temporal filter of alpha (otvm_amd/temporal.py) behind the frame -- and behind
+    _WorkingResolution.finish -- on the launch stream.  refuse() is the host-only part, before anything is uploaded."""
+
+    def __init__(self, options, frames_are_rgb):
+        self.options, self.rgb, self.filter = options, bool(frames_are_rgb), None
+
+    @staticmethod
+    def refuse(plan, frames, backgrounds):
+        if backgrounds is not None:
+            raise ValueError("run_video_matte: stabilise takes no per-frame `backgrounds`: the flow is taken between the frames "
+                             "as they are staged, and with `backgrounds` the network mattes their composite, which is not staged")
+        if not plan.natural:
+            raise ValueError("run_video_matte: stabilise needs the frames in natural order (the filter is causal: each frame "
+                             "leans on the one before it); this keyframe schedule sweeps backward from frame %d" % plan.k0)
+        if (len(frames) > 0 and (isinstance(frames, (list, tuple, np.ndarray)) or torch.is_tensor(frames))
+                and _as_tensor(frames[0]).dtype != torch.uint8):
+            raise ValueError("run_video_matte: stabilise takes uint8 [H,W,3] frames (the flow is OpenCV's Farneback flow of the "
+                             "8-bit grey frames; float frames have no such route), got %s" % _as_tensor(frames[0]).dtype)
+
+    def check_frame(self, f):
+        """(a streaming source is checked frame by frame)"""
+        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != 3:
+            raise ValueError("run_video_matte: stabilise takes uint8 [H,W,3] frames (the flow is OpenCV's Farneback flow of the "
+                             "8-bit grey frames; float frames have no such route), got %s %s" % (f.dtype, tuple(f.shape)))
+
+    def step(self, frame, alpha, trimap, tri_scale, dev):
+        """(stabilised alpha, its byte) of the frame staged on the device [H,W,3], its raw alpha [H,W] and the trimap the
+        network put out [3,h,w]"""
+        from .temporal import TemporalStabiliser
+        H, W = alpha.shape
+        if self.filter is None or (self.filter.H, self.filter.W) != (H, W):
+            self.filter = TemporalStabiliser(dev, H, W, **self.options)
+        return self.filter.step(frame, alpha, trimap=trimap, tri_scale=tri_scale, rgb=self.rgb)
 
 
 class _Collector:
@@ -352,9 +393,10 @@ class _Collector:
     kept where it is with ``keep_on_device`` and brought to the host as it comes otherwise.  With ``on_foreground`` the foreground
     frames are handed over and none is kept."""
 
-    def __init__(self, T, keep_on_device, foreground, composite, on_foreground=None):
+    def __init__(self, T, keep_on_device, foreground, composite, on_foreground=None, raw=False):
         self.keep = (lambda x: x) if keep_on_device else (lambda x: x.cpu())
         self.alpha, self.u8, self.trimap, self.bank, self.anchors = ([None] * T for _ in range(5))
+        self.raw = [None] * T if raw else None            # ``stabilise``: the alpha before the temporal filter
         self.on_foreground = on_foreground if foreground else None
         self.rgba = [None] * T if foreground and on_foreground is None else None
         self.comp = [None] * T if self.rgba is not None and composite else None
@@ -363,8 +405,10 @@ class _Collector:
         """The frame ids resident after frame ``i``'s update, and those of them that are anchors (host lists)."""
         self.bank[i], self.anchors[i] = list(frames), list(anchors)
 
-    def put(self, i, alpha, u8, trimap, rgba=None, comp=None):
+    def put(self, i, alpha, u8, trimap, rgba=None, comp=None, raw=None):
         self.alpha[i], self.u8[i], self.trimap[i] = self.keep(alpha), self.keep(u8), self.keep(trimap)
+        if self.raw is not None:
+            self.raw[i] = self.keep(raw)
         if self.on_foreground is not None:
             self.on_foreground(i, rgba, comp)
         if self.rgba is not None:
@@ -379,6 +423,8 @@ class _Collector:
             res.update(anchor_frames=self.anchors, schedule=schedule)
         if work_size is not None:
             res["work_size"] = work_size
+        if self.raw is not None:
+            res["alpha_raw"] = torch.stack(self.raw)
         if self.rgba is not None:
             res["fgr_u8"] = torch.stack(self.rgba)
         if self.comp is not None:
@@ -392,7 +438,7 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                     frames_are_rgb=False, on_frame=None, device=None, keep_on_device=False, gt_alpha_u8=None,
                     gt_mask_u8=None, gt_mask=None, gt_image_metrics=False, gt_flow_metrics=False, foreground=False,
                     new_background=None, keyframes=None, work_scale=None, work_radius=2, work_eps=1e-4, on_foreground=None,
-                    mask=None, masks=None):
+                    mask=None, masks=None, stabilise=None):
     """Matte one sequence.
 
     model       : EvalModel (optionally wrapped in nn.DataParallel), on the GPU
@@ -442,6 +488,18 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                   so the STM query encoder, memory read, decoder and Encoder_M never run and the bank stays empty (bank_frames
                   is [] for every frame).  Exclusive with trimap, mask, keyframes and alphas; on_frame, the metrics, foreground
                   and new_background work as in any clip.  Not available in run_video_matte_batch.
+    stabilise   : None (off: a frame issues exactly the launches it issues without the option), True, a strength in [0,1], or a
+                  dict of temporal.TemporalStabiliser's keywords (strength, tau_colour, tau_alpha, region): temporal
+                  stabilisation of alpha, a causal flow-compensated recursive filter on the launch stream behind each frame
+                  (and behind the guided upsampling of ``work_scale``, at H x W).  The previous stabilised alpha is fetched where
+                  the Farneback flow of the grey frames points and blended in where the colours agree, alpha has not really
+                  changed and -- region="unknown" -- the frame's trimap says unknown.  alpha, alpha_u8, on_frame's alpha / u8 and
+                  the metrics carry the stabilised values, the result gains alpha_raw [T,H,W] (the alpha before the filter), and
+                  with ``foreground`` / ``new_background`` the bytes are remade from the stabilised alpha and the frame's F
+                  (fgr_u8[..., 3] == alpha_u8).  There is no trained checkpoint here: the filter is checked by definition and by
+                  property on synthetic clips, not by quality on real footage, and the default parameters are PLACEHOLDERS.
+                  Refused for float frames, with ``backgrounds`` and for a keyframe schedule that is not in natural order (a
+                  backward sweep); not available in run_video_matte_batch.
     Returns dict(alpha=[T,H,W] float32, alpha_u8=[T,H,W] uint8 (truncated, eval.py:209), trimap=[T,3,H,W],
     bank_frames=[per frame: ids of the frames resident in the memory bank after that frame's update]) and, when ``keyframes``
     was given, anchor_frames=[per frame: those of them that are anchors], schedule=[the steps issued, keyframe_schedule's tuples].
@@ -451,11 +509,15 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
     dev = device or next(model.parameters()).device
     plan = _ClipPlan(model, frames, trimap, alphas, keyframes, mask, masks, backgrounds, work_scale, work_radius, work_eps, skip,
                      max_num)
+    stab = temporal.options_of(stabilise)
+    if stab is not None:
+        _Stabilisation.refuse(plan, frames, backgrounds)
+        stab = _Stabilisation(stab, frames_are_rgb)
     core = model.module if hasattr(model, "module") else model
     foreground = bool(foreground) or new_background is not None
     work = (None if work_scale is None else
             _WorkingResolution(work_scale, work_radius, work_eps, foreground, frames_are_rgb, new_background))
-    col = _Collector(T, keep_on_device, foreground, new_background is not None, on_foreground)
+    col = _Collector(T, keep_on_device, foreground, new_background is not None, on_foreground, raw=stab is not None)
     metrics = (ClipMetrics(dev, image_metrics=gt_image_metrics, flow_metrics=gt_flow_metrics) if gt_alpha_u8 is not None
                else None)
     plan.upload(dev)
@@ -464,6 +526,8 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
         for i, kind, first_frame, last_frame, step_memorize in plan.steps:
             f = _as_tensor(frames[i])
             b = _as_tensor(backgrounds[i]) if backgrounds is not None else None
+            if stab is not None:
+                stab.check_frame(f)
             fg, bg, H, W, rgb_applies, ready, ready_b = (work.stage(f, dev) if work is not None else
                                                          _stage_frame(f, b, dev, frames_are_rgb))
             extra = {"_frames_rgb": bool(frames_are_rgb)} if rgb_applies else {}
@@ -488,22 +552,36 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                 memorize = step_memorize
             if foreground:
                 # (working resolution: the composite is made at full resolution by work.finish, not by the engine)
-                core.set_background(None if new_background is None or work is not None
+                # (stabilise: made behind the temporal filter, from the stabilised alpha)
+                core.set_background(None if new_background is None or work is not None or stab is not None
                                     else _background_at(new_background, i, dev, bg_cache))
             out = model(a, fg, bg, tri=None, tri_gt=tri_gt, first_frame=first_frame, last_frame=last_frame,
                         memorize=memorize, max_memory_num=max_memory_num, large_input=large, _frame_id=i, **extra, **more)
             alpha, u8, rgba, comp = out[3][0, 0, 0], core._engine.last_alpha_u8, None, None
             if work is not None:
-                alpha, u8, rgba, comp = work.finish(i, fg, alpha, core._engine, dev)
+                alpha, u8, rgba, comp = work.finish(i, fg, alpha, core._engine, dev, make_bytes=stab is None)
             elif foreground:
                 rgba, comp = core._engine.last_rgba_u8, core._engine.last_comp_u8
+            raw = None
+            if stab is not None:
+                # the frame as it was staged (its upload is behind the launch stream: the model waited for it), the alpha at
+                # H x W and the trimap the network put out, at the resolution it ran at
+                raw = alpha
+                alpha, u8 = stab.step(fg if work is None else work.full, alpha, out[1][0, 0], 1 if work is None else work_scale, dev)
+                if work is not None and foreground:
+                    rgba, comp = work.foreground_bytes(i, alpha, dev)
+                elif foreground:
+                    nb = None if new_background is None else _background_at(new_background, i, dev, bg_cache)
+                    if isinstance(nb, tuple):
+                        background_colour(nb, "run_video_matte")
+                    rgba, comp = guided.foreground_bytes(alpha, core._engine.last_fgr, frames_are_rgb, nb, "run_video_matte")
             mem_now = core.memories
             col.log_bank(i, mem_now["frames"], mem_now["anchors"])
             if metrics is not None and plan.natural:
                 _metrics_add(metrics, u8, i, gt_alpha_u8, gt_mask_u8, gt_mask, dev)
             if on_frame is not None:
                 on_frame(i, alpha, u8, out)
-            col.put(i, alpha, u8, out[1][0, 0], rgba, comp)
+            col.put(i, alpha, u8, out[1][0, 0], rgba, comp, raw=raw)
     if metrics is not None and not plan.natural:
         # the pair terms (dtSSD, MESSDdt) depend on the order: fed in natural frame order from the kept 8-bit alphas
         for i in range(T):
