@@ -70,7 +70,9 @@ const char* otvm_last_error(void);
                                   otvm_guided_coeffs and otvm_guided_apply with their struct otvm_guided_params;
                                   likewise trimaps from masks: otvm_trimap_from_mask / _ws_bytes with otvm_mask_trimap_params;
                                   likewise the temporal stabilisation of alpha: otvm_luma_u8 and otvm_temporal_blend with
-                                  otvm_temporal_params) */
+                                  otvm_temporal_params;
+                                  likewise the patch conv with an upsampled source: otvm_conv2d_up and
+                                  otvm_conv2d_accepts_upsampled_input with otvm_conv_up_params) */
 int otvm_abi_version(void);
 
 /* ---------------------------------------------------------------- weights (load time) ----------
@@ -215,6 +217,29 @@ int otvm_conv2d_accepts_input_norm(const otvm_conv_params* p);
 /* 0 = no kernel takes it, 1 = the patch kernel would run this layer, 2 = an implicit-GEMM tile (which normalises every input
  * element once per tap: worth it for 1x1 layers, not for 3x3 layers with many channels -- the host's choice).  (ABI 16) */
 int otvm_conv2d_input_norm_kind(const otvm_conv_params* p);
+
+/* (21, additive: new symbols only.)  A 3x3 patch-kernel conv whose LEADING Cu input channels are the 2x bilinear upsampling
+ * (align_corners = False) of a source-resolution tensor, interpolated while the conv stages its input patch: the 4x copy that
+ * otvm_upsample_bilinear_b would write into channels [0, Cu) of the conv's input is never made.  Input channels [0, Cu) of the
+ * weights meet the upsampled source, channels [Cu, p->Cin) the full-resolution view p->in, whose FIRST channel is input channel Cu
+ * (p->in_ld / p->in_bs as usual; p->Cin stays the layer's whole padded channel count).  Each source element is normalised
+ * (scale / shift / act: a GroupNorm table as otvm_upsample_bilinear_b takes it, or NULL) once, then blended with the arithmetic of
+ * that kernel: the output -- and the fused GroupNorm sums -- equal, bit for bit, those of the pass followed by otvm_conv2d.
+ * Taken by: f16x3 / f16, 3x3, stride 1, dilation 1, Cout <= 64 (the 64-filter and 32-filter patch tiles), p->H == 2 Hi and
+ * p->W == 2 Wi, Cu % 16 == 0, no in_scale / in_relu / in_res on p, tune 0 or the patch kernel's code, 16-byte aligned views.  */
+typedef struct otvm_conv_up_params {
+    const float* src; int Hi, Wi, Cu, src_ld;       /* [Hi][Wi][Cu] at pixel stride src_ld                                    */
+    int64_t src_bs;                                 /* floats between the images' sources (p->batch > 1)                      */
+    const float* scale; const float* shift;         /* optional: src' = act(src * scale[c] + shift[c]), Cu floats each         */
+    int act;                                        /* OTVM_ACT_* after the normalisation                                     */
+    int norm_bs;                                    /* floats between the images' tables                                       */
+    int tile_rows;                                  /* 0 = the tile otvm_conv2d picks for the map; 16 = the 16x32-pixel tile of the
+                                                       <= 32-filter layers whatever the map size (same bits either way)        */
+} otvm_conv_up_params;
+int otvm_conv2d_up(const otvm_conv_params* p, const otvm_conv_up_params* u, void* stream);
+/* 1 when otvm_conv2d_up takes (p, u), else 0 (wrong tile family, Cu % 16 != 0, a map that is not exactly 2x the source,
+ * unaligned views, ...); launches nothing.                                                                                   */
+int otvm_conv2d_accepts_upsampled_input(const otvm_conv_params* p, const otvm_conv_up_params* u);
 
 /* f16x3: derive the split weights from a packed fp32 weight (see otvm_pack_conv_weight):
  * row o is scaled by 2^-e (|w| <= 1), w_hi = fp16(w), w_lo = fp16(w - w_hi), w_scale[o] = 2^e.

@@ -18,6 +18,7 @@
 #include "common.h"
 #include "head_math.h"
 #include "f16x3_ops.h"
+#include "upfold_index.h"
 #include <type_traits>
 #include <stdlib.h>
 
@@ -71,6 +72,10 @@ struct PatchArgs {
     // ABI 17 (HEAD kernels, 16 output channels): the 1x1 head + fba_fusion of the FBA decoder / refinement run in the epilogue
     // on the pixel's 16 hidden values (head_math.h); out (the hidden state) is optional then
     OtvmHeadArgs head; int64_t head_img_bs, head_alpha_bs, head_tri_bs, head_sm_bs, head_fgr_bs;
+    // UP kernels (otvm_conv2d_up): input channels [0, 16 up_ncb) are the 2x bilinear upsampling of up_src [up_Hi][up_Wi] (pixel stride
+    // up_ld), each source element normalised with up_scale / up_shift / up_act (nullptr: plain) first; `in` is the view of the other channels
+    const float* up_src; const float* up_scale; const float* up_shift;
+    int up_Hi, up_Wi, up_ld, up_ncb, up_act, up_norm_bs; int64_t up_bs; unsigned up_bytes;
 };
 
 constexpr int CB = 16;           // channels per stage = one MFMA k-step
@@ -96,6 +101,24 @@ __device__ __forceinline__ int pi16(int r) {
     return 4 * (k >> 1) + (k & 1) + ((r >= 4 && r < 12) ? 2 : 0);
 }
 
+// ---- UP (otvm_conv2d_up): the arithmetic of upsample_bilinear_kernel / upsample2x_bilinear_kernel (resample.hip, built with
+// -ffp-contract=off; this file is not): every step a single IEEE operation, in that kernel's order
+__device__ __forceinline__ f32x4 otvm_up_norm(const f32x4 x, const f32x4 sc, const f32x4 sh, int act) {
+#pragma clang fp contract(off)
+    f32x4 v = x * sc;
+    v = v + sh;
+    v.x = otvm_act(v.x, act); v.y = otvm_act(v.y, act); v.z = otvm_act(v.z, act); v.w = otvm_act(v.w, act);
+    return v;
+}
+__device__ __forceinline__ f32x4 otvm_up_blend(const f32x4 v00, const f32x4 v01, const f32x4 v10, const f32x4 v11, float lx, float ly) {
+#pragma clang fp contract(off)
+    const float hx = 1.f - lx, hy = 1.f - ly;
+    const f32x4 a0 = hx * v00, a1 = lx * v01, b0 = hx * v10, b1 = lx * v11;
+    const f32x4 a = a0 + a1, b = b0 + b1;
+    const f32x4 ta = hy * a, tb = ly * b;
+    return ta + tb;
+}
+
 // Per stage (16 input channels) a workgroup holds in LDS the split input patch and, per group of TAPG taps, the B
 // fragments of its BN output channels, copied verbatim from the fragment-major weight array (1-KiB blocks).
 // TAPG = 9: one weight stage per channel stage (narrow layers); TAPG = 3: wide layers (BN = 256), where nine taps of
@@ -113,8 +136,14 @@ __device__ __forceinline__ int pi16(int r) {
 // fragment ({0-3, 12-15, 20-27}, ...: rows {0-3, 12-15} of one octet + rows 4-11 of the other) covers sixteen distinct 16-byte
 // bank slots for ANY tap offset, and the staging ds_write_b64 (four pixels x four quads per 16 lanes) is conflict-free too.
 // B fragments come from the unchanged 1-KiB blocks: slot (lane & 15) + 16 sj + 32 (octet & 1) of tap t or t + 1.
+// UP (otvm_conv2d_up): the stages of the leading input channels stage the 2x bilinear upsampling of a source-resolution tensor.  Per
+// such stage a workgroup loads the (TH / 2 + 2) x 18 source pixels its patch needs (halo included), normalises and activates each
+// element ONCE and parks it in an fp32 LDS scratch (6.9 KB for 8 x 32 pixels, 11.5 KB for 16 x 32); after a barrier every thread
+// blends the four neighbours of its own patch elements out of the scratch (indices, slots and weights: upfold_index.h, computed once
+// per thread) and splits / stores them exactly as a stage loaded at full resolution.  Fine pixels outside the image are the conv's zero
+// padding, not interpolated.  One uniform branch per stage; the MFMA section, the weight stages and the epilogues do not know.
 template <int TH, int BN, int NW, int DIL, int TAPG, bool INRES = false, bool HEAD = false, int NWN = 1, bool GLDS = false, int NPASS = 3,
-          bool M16 = false, bool FGR = false>
+          bool M16 = false, bool FGR = false, bool UP = false>
 __global__ __launch_bounds__(NW * 64)
 __attribute__((amdgpu_waves_per_eu((TAPG == 3 && BN <= 32 && !INRES) ? 3 : (M16 ? 2 : 1), (TAPG == 3 && BN <= 32 && !INRES) ? 3 : 10)))
 void conv_patch_f16x3_kernel(const PatchArgs pa) {
@@ -134,6 +163,10 @@ void conv_patch_f16x3_kernel(const PatchArgs pa) {
         if (p.residual) p.residual += zb * p.res_bs;
         if (p.gn_stats) p.gn_stats += zb * p.gn_bs;
         if (p.in_scale) { p.in_scale += zb * p.norm_bs; p.in_shift += zb * p.norm_bs; }
+        if constexpr (UP) {
+            p.up_src += zb * p.up_bs;
+            if (p.up_scale) { p.up_scale += zb * p.up_norm_bs; p.up_shift += zb * p.up_norm_bs; }
+        }
     }
     constexpr int NT = NW * 64;
     // NWN = 1: a wave owns TM = TH / NW output rows x all BN / 32 channel tiles.  NWN > 1 (the 256-channel tiles, round 4): the
@@ -160,11 +193,16 @@ void conv_patch_f16x3_kernel(const PatchArgs pa) {
     // (LDS-DMA weight stages copy every channel tile of the block: the host offers them to layers with Cout % BN == 0 only)
     static_assert(!GLDS || TAPG == 3, "LDS-DMA weight stages: the 3-tap stages (two buffers fit beside the patch)");
     constexpr int NBUF = GLDS ? 2 : 1;
-    constexpr int SM_HALFS = PATCH_HALFS + NBUF * B_HALFS > EPI_HALFS ? PATCH_HALFS + NBUF * B_HALFS : EPI_HALFS;
+    static_assert(!UP || (DIL == 1 && !INRES && !HEAD && !GLDS && NWN == 1 && TH % 2 == 0), "upsampled source: the plain dilation-1 tiles");
+    // UP: the source patch of a stage, [USH x USW source pixels][16 channels] fp32, behind the weight stage
+    constexpr int USH = otvm_upfold_extent(TH), USW = otvm_upfold_extent(32), NSPIX = USH * USW;
+    constexpr int UP_HALFS = UP ? NSPIX * CB * 2 : 0;
+    constexpr int SM_HALFS = PATCH_HALFS + NBUF * B_HALFS + UP_HALFS > EPI_HALFS ? PATCH_HALFS + NBUF * B_HALFS + UP_HALFS : EPI_HALFS;
     __shared__ __attribute__((aligned(16))) _Float16 smem[SM_HALFS];
     _Float16* Ph = smem;
     _Float16* Pl = smem + (M16 ? 2 * PLANE * 8 : NPIX * LDP);
     _Float16* Bs = smem + PATCH_HALFS;
+    float* Us = reinterpret_cast<float*>(smem + PATCH_HALFS + NBUF * B_HALFS);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wave_m = NWN == 1 ? wave : wave % NWM, nt0 = NWN == 1 ? 0 : (wave / NWM) * TN;   // first row block / channel tile of the wave
@@ -240,12 +278,83 @@ void conv_patch_f16x3_kernel(const PatchArgs pa) {
         l_o0 = (((tid >> 1) & 1) * PLANE + (tid >> 2)) * 8 + (tid & 1) * 4;
         l_slope = p.in_relu ? 0.f : (p.in_scale ? (p.in_act == OTVM_ACT_RELU ? 0.f : (p.in_act == OTVM_ACT_LEAKY ? 0.01f : 1.f)) : 1.f);
     }
-    auto prefetch = [&](int cb, int g) __attribute__((always_inline)) {
-        if constexpr (LEAN) {
-            const unsigned soff = (unsigned)(cb * CB * 4);
+    // ---- UP: what a source stage needs from this thread, computed once
+    constexpr int NS = (NSPIX * 4 + NT - 1) / NT;                      // source-patch float4 per thread
+    static_assert(NS <= NP, "the source patch is loaded into the patch registers");
+    const int up_ncb = UP ? p.up_ncb : 0;
+    __amdgpu_buffer_rsrc_t up_rsrc = otvm_buffer_rsrc(UP ? p.up_src : p.in, UP ? p.up_bytes : 0);
+    unsigned u_voff[UP ? NS : 1];                                      // byte offset of source element k's quad in channel block 0; 0xFFFFFFFF = outside the source / patch
+    unsigned u_inf[UP ? NP : 1];                                       // patch element k: bits 0-7 scratch slot of (y0, x0); 8 / 9: x1 / y1 one slot further; 10-11 / 12-13:
+                                                                       // 4 lx / 4 ly; 14: inside the image
+    if constexpr (UP) {
+        const int sy0 = otvm_upfold_origin(ty0), sx0 = otvm_upfold_origin(tx0);
 #pragma unroll
-            for (int k = 0; k < NP; ++k)
-                rp[k] = __builtin_bit_cast(f32x4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(in_rsrc, __builtin_elementwise_add_sat(l_voff[k], soff), 0, 0));   // (saturating: outside stays outside)
+        for (int k = 0; k < NS; ++k) {
+            const int idx = tid + k * NT;
+            const int spix = idx >> 2, c4 = (idx & 3) * 4;
+            const int sr = spix / USW, sc = spix - sr * USW;
+            const int sy = sy0 + sr, sx = sx0 + sc;
+            const bool ok = ((unsigned)sy < (unsigned)p.up_Hi) & ((unsigned)sx < (unsigned)p.up_Wi) & (idx < NSPIX * 4);
+            u_voff[k] = ok ? ((unsigned)(sy * p.up_Wi + sx) * (unsigned)p.up_ld + (unsigned)c4) << 2 : 0xFFFFFFFFu;
+        }
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+            const int idx = tid + k * NT;
+            const int pix = idx >> 2;
+            const int py = pix / PW, px = pix - py * PW;
+            const int iy = ty0 - DIL + py, ix = tx0 - DIL + px;
+            const OtvmUpAxis ay = otvm_upfold_axis(iy, p.up_Hi, sy0, USH), ax = otvm_upfold_axis(ix, p.up_Wi, sx0, USW);
+            const bool inside = ((unsigned)iy < (unsigned)p.H) & ((unsigned)ix < (unsigned)p.W);
+            u_inf[k] = (unsigned)(ay.s0 * USW + ax.s0) | ((unsigned)(ax.s1 - ax.s0) << 8) | ((unsigned)(ay.s1 - ay.s0) << 9) |
+                       ((unsigned)ax.code << 10) | ((unsigned)ay.code << 12) | (inside ? 1u << 14 : 0u);
+        }
+    }
+    // UP, a source stage: this thread's share of the source patch -> (normalised) -> scratch; barrier; rp[k] = the blended patch elements
+    auto up_fill = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            const int idx = tid + k * NT;
+            if (k + 1 < NS || idx < NSPIX * 4) {
+                f32x4 v = rp[k];
+                if (p.up_scale) v = otvm_up_norm(v, rsc, rsh, p.up_act);          // (uniform)
+                *reinterpret_cast<f32x4*>(&Us[idx * 4]) = v;
+            }
+        }
+        __syncthreads();
+        const int q4 = (tid & 3) * 4;                                   // (NT % 4 == 0: the channel quad of element k is tid & 3 for every k)
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+            unsigned inf = u_inf[UP ? k : 0];
+            // (opaque: everything decoded from it is loop-invariant, and hoisted out of the K loop it is nine registers per element
+            // instead of one -- the 64-filter tile then needs 366 registers and loses its second workgroup per CU)
+            asm volatile("" : "+v"(inf));
+            const int o00 = (int)(inf & 255u) * CB + q4, dx = (int)((inf >> 8) & 1u) * CB, dy = (int)((inf >> 9) & 1u) * (USW * CB);
+            const f32x4 v00 = *reinterpret_cast<const f32x4*>(&Us[o00]), v01 = *reinterpret_cast<const f32x4*>(&Us[o00 + dx]);
+            const f32x4 v10 = *reinterpret_cast<const f32x4*>(&Us[o00 + dy]), v11 = *reinterpret_cast<const f32x4*>(&Us[o00 + dy + dx]);
+            const float lx = 0.25f * (float)((inf >> 10) & 3u), ly = 0.25f * (float)((inf >> 12) & 3u);
+            const f32x4 v = otvm_up_blend(v00, v01, v10, v11, lx, ly);
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            rp[k] = ((inf >> 14) & 1u) ? v : z;                         // the conv's zero padding is not interpolated
+        }
+    };
+    auto prefetch = [&](int cb, int g) __attribute__((always_inline)) {
+        const bool src_stage = UP && cb < up_ncb;                       // (uniform)
+        if constexpr (LEAN) {
+            if (src_stage) {
+                const unsigned soff = (unsigned)(cb * CB * 4);
+#pragma unroll
+                for (int k = 0; k < NS; ++k)
+                    rp[k] = __builtin_bit_cast(f32x4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(up_rsrc, __builtin_elementwise_add_sat(u_voff[UP ? k : 0], soff), 0, 0));
+                if (p.up_scale) {
+                    rsc = *reinterpret_cast<const f32x4*>(p.up_scale + cb * CB + (tid & 3) * 4);
+                    rsh = *reinterpret_cast<const f32x4*>(p.up_shift + cb * CB + (tid & 3) * 4);
+                }
+            } else {
+                const unsigned soff = (unsigned)((cb - up_ncb) * CB * 4);   // (UP: `in` is the view of the channels behind the upsampled ones)
+#pragma unroll
+                for (int k = 0; k < NP; ++k)
+                    rp[k] = __builtin_bit_cast(f32x4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(in_rsrc, __builtin_elementwise_add_sat(l_voff[k], soff), 0, 0));   // (saturating: outside stays outside)
+            }
             const char* wbase = reinterpret_cast<const char*>(p.wf) + (size_t)(((cb >> 1) * 9 * nbs * 2 + (cb & 1)) * 2) * 1024;   // uniform
 #pragma unroll
             for (int k = 0; k < NB; ++k) rb[k] = *reinterpret_cast<const f16x8*>(wbase + l_woff[k]);
@@ -282,11 +391,20 @@ void conv_patch_f16x3_kernel(const PatchArgs pa) {
                 }
             }
         }
-        if (g == 0) {
+        if (g == 0 && src_stage) {
+            if (p.up_scale) {
+                rsc = *reinterpret_cast<const f32x4*>(p.up_scale + cb * CB + (tid & 3) * 4);
+                rsh = *reinterpret_cast<const f32x4*>(p.up_shift + cb * CB + (tid & 3) * 4);
+            }
+#pragma unroll
+            for (int k = 0; k < NS; ++k)
+                rp[k] = __builtin_bit_cast(f32x4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(up_rsrc, __builtin_elementwise_add_sat(u_voff[UP ? k : 0], (unsigned)(cb * CB * 4)), 0, 0));
+        } else if (g == 0) {
             if (p.in_scale) {                                           // NT % 4 == 0: idx & 3 == tid & 3 for every k
                 rsc = *reinterpret_cast<const f32x4*>(p.in_scale + cb * CB + (tid & 3) * 4);
                 rsh = *reinterpret_cast<const f32x4*>(p.in_shift + cb * CB + (tid & 3) * 4);
             }
+            const int cbv = cb - up_ncb;                                // (UP: `in` is the view of the channels behind the upsampled ones)
 #pragma unroll
             for (int k = 0; k < NP; ++k) {
                 const int idx = tid + k * NT;
@@ -298,18 +416,20 @@ void conv_patch_f16x3_kernel(const PatchArgs pa) {
                 const unsigned oob = (unsigned)((int)((unsigned)iy < (unsigned)p.H) & (int)((unsigned)ix < (unsigned)p.W) &
                                                 (int)(idx < NPIX * 4)) - 1u;
                 const unsigned e = (unsigned)(iy * p.W + ix);
-                rp[k] = __builtin_bit_cast(f32x4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(in_rsrc, ((e * (unsigned)p.in_ld + cb * CB + c4) << 2) | oob, 0, 0));
+                rp[k] = __builtin_bit_cast(f32x4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(in_rsrc, ((e * (unsigned)p.in_ld + cbv * CB + c4) << 2) | oob, 0, 0));
                 if (INRES)
                     rr[k] = __builtin_bit_cast(f32x4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(res_rsrc, ((e * (unsigned)p.in_res_ld + cb * CB + c4) << 2) | oob, 0, 0));
             }
         }
     };
-    auto commit = [&](int g) __attribute__((always_inline)) {
+    auto commit = [&](int cb, int g) __attribute__((always_inline)) {
+        const bool src_stage = UP && cb < up_ncb;                       // (uniform)
         if constexpr (LEAN) {
             const f16x8 zero8 = {(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
 #pragma unroll
             for (int k = 0; k < NB; ++k) *reinterpret_cast<f16x8*>(&Bs[(tid + k * NT) * 8]) = ((l_wok >> k) & 1u) ? rb[k] : zero8;
-            if (p.in_scale != nullptr || p.in_relu) {                   // ONE uniform branch per stage; rsc = 1, rsh = 0 without a table
+            if (src_stage) up_fill();
+            else if (p.in_scale != nullptr || p.in_relu) {              // ONE uniform branch per stage; rsc = 1, rsh = 0 without a table
 #pragma unroll
                 for (int k = 0; k < NP; ++k) {
                     f32x4 v = rp[k] * rsc + rsh;
@@ -339,6 +459,7 @@ void conv_patch_f16x3_kernel(const PatchArgs pa) {
             }
         }
         if (g == 0) {
+            if (src_stage) up_fill();                                   // (UP kernels take no in_scale / in_relu: the values go to the split as they are)
 #pragma unroll
             for (int k = 0; k < NP; ++k) {
                 const int idx = tid + k * NT;
@@ -387,12 +508,12 @@ void conv_patch_f16x3_kernel(const PatchArgs pa) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's share of the stage's weights has landed
                 __syncthreads();                                        // ... everybody's; and the previous stage's LDS reads are done
                 if (g == 0) {                                           // a new input patch (every third stage)
-                    commit(0);
+                    commit(cb, 0);
                     __syncthreads();
                 }
             } else {
                 __syncthreads();                                        // the previous stage's LDS reads are done
-                if (!OTVM_PABL_NOCOMMIT || (cb == 0 && g == 0)) commit(g);
+                if (!OTVM_PABL_NOCOMMIT || (cb == 0 && g == 0)) commit(cb, g);
                 __syncthreads();
             }
             if (!OTVM_PABL_NOLOAD) {
@@ -858,13 +979,13 @@ __global__ __launch_bounds__(256) void pack_patch_weight_kernel(const float* __r
 }
 
 template <int NPASS, int TH, int BN, int NW, int DIL, int TAPG = 9, bool INRES = false, bool HEAD = false, int NWN = 1, bool GLDS = false,
-          bool M16 = false, bool FGR = false>
+          bool M16 = false, bool FGR = false, bool UP = false>
 int launch_patch(PatchArgs& a, hipStream_t s) {
     a.tiles_x = otvm_ceil_div(a.W, 32);
     a.tiles_y = otvm_ceil_div(a.H, TH);
     a.tiles_n = otvm_ceil_div(a.Cout, BN);
     a.walk = otvm_tile_walk_of(1);
-    hipLaunchKernelGGL((conv_patch_f16x3_kernel<TH, BN, NW, DIL, TAPG, INRES, HEAD, NWN, GLDS, NPASS, M16, FGR>), dim3(a.tiles_x * a.tiles_y * a.tiles_n, a.batch), dim3(NW * 64), 0, s, a);
+    hipLaunchKernelGGL((conv_patch_f16x3_kernel<TH, BN, NW, DIL, TAPG, INRES, HEAD, NWN, GLDS, NPASS, M16, FGR, UP>), dim3(a.tiles_x * a.tiles_y * a.tiles_n, a.batch), dim3(NW * 64), 0, s, a);
     OTVM_CHECK_LAUNCH("otvm_conv2d(patch f16x3)");
     return 0;
 }
@@ -928,7 +1049,7 @@ int otvm_conv2d_patch_eligible(const otvm_conv_params* p) {
 }
 
 static int patch_run(const otvm_conv_params* p, void* stream, int choice, const otvm_head_params* hd = nullptr, float* fgr = nullptr,
-                     int64_t fgr_bs = 0);
+                     int64_t fgr_bs = 0, const otvm_conv_up_params* up = nullptr);
 int otvm_conv2d_head16_impl(const otvm_conv_params* p, const otvm_head_params* hd, float* fgr, int64_t fgr_bs, void* stream);   // conv_head16_f16x3.hip
 
 // ABI 17: 3x3 conv to 16 channels with the FBA head in its epilogue (include/otvm_hip.h); fgr != nullptr: otvm_conv2d_head_fgr
@@ -967,7 +1088,8 @@ static int patch_m16() {
 }
 
 template <int NPASS>
-static int patch_run_t(const otvm_conv_params* p, void* stream, int choice, const otvm_head_params* hd, float* fgr, int64_t fgr_bs) {
+static int patch_run_t(const otvm_conv_params* p, void* stream, int choice, const otvm_head_params* hd, float* fgr, int64_t fgr_bs,
+                       const otvm_conv_up_params* up) {
     if (choice == 0) return -1;
     const bool is_wide = choice == 2;
     PatchArgs a;
@@ -986,6 +1108,21 @@ static int patch_run_t(const otvm_conv_params* p, void* stream, int choice, cons
         const int64_t ib = (int64_t)p->H * p->W * p->in_ld * 4, rb = p->in_res ? (int64_t)p->H * p->W * p->in_res_ld * 4 : 0;
         OTVM_REQUIRE(ib < 0xFFFFFFF0ll && rb < 0xFFFFFFF0ll, "otvm_conv2d(patch f16x3): input view of %lld bytes is beyond 32-bit offsets", (long long)ib);
         a.in_bytes = (unsigned)ib; a.in_res_bytes = (unsigned)rb;
+    }
+    a.up_src = nullptr; a.up_scale = a.up_shift = nullptr;
+    a.up_Hi = a.up_Wi = a.up_ld = a.up_ncb = a.up_act = a.up_norm_bs = 0; a.up_bs = 0; a.up_bytes = 0;
+    if (up) {   // otvm_conv2d_up (arguments checked by otvm_conv2d_accepts_upsampled_input): the tile otvm_conv2d runs, with the source stages
+        a.up_src = up->src; a.up_scale = up->scale; a.up_shift = up->shift; a.up_act = up->act;
+        a.up_Hi = up->Hi; a.up_Wi = up->Wi; a.up_ld = up->src_ld; a.up_ncb = up->Cu / CB;
+        a.up_bs = a.batch > 1 ? up->src_bs : 0; a.up_norm_bs = a.batch > 1 ? up->norm_bs : 0;
+        a.up_bytes = (unsigned)((int64_t)up->Hi * up->Wi * up->src_ld * 4);
+        if (p->Cout <= 32) {
+            if (up->tile_rows == 16 || (up->tile_rows == 0 && (int64_t)p->H * p->W >= (1 << 20)))
+                return launch_patch<NPASS, 16, 32, 4, 1, 3, false, false, 1, false, false, false, true>(a, s);
+            return launch_patch<NPASS, 8, 32, 4, 1, 3, false, false, 1, false, false, false, true>(a, s);
+        }
+        if constexpr (NPASS == 3) return launch_patch<3, 8, 64, 4, 1, 9, false, false, 1, false, true, false, true>(a, s);
+        else return launch_patch<NPASS, 8, 64, 4, 1, 9, false, false, 1, false, false, false, true>(a, s);
     }
     if (hd) {
         a.head.w = hd->w; a.head.b = hd->b; a.head.n_out = hd->n_out; a.head.img = hd->img; a.head.img_ld = hd->img_ld;
@@ -1055,6 +1192,39 @@ static int patch_run_t(const otvm_conv_params* p, void* stream, int choice, cons
     return launch_patch<NPASS, 8, 64, 4, 4>(a, s);
 }
 
-static int patch_run(const otvm_conv_params* p, void* stream, int choice, const otvm_head_params* hd, float* fgr, int64_t fgr_bs) {
-    return p->precision == OTVM_PREC_F16 ? patch_run_t<1>(p, stream, choice, hd, fgr, fgr_bs) : patch_run_t<3>(p, stream, choice, hd, fgr, fgr_bs);
+static int patch_run(const otvm_conv_params* p, void* stream, int choice, const otvm_head_params* hd, float* fgr, int64_t fgr_bs,
+                     const otvm_conv_up_params* up) {
+    return p->precision == OTVM_PREC_F16 ? patch_run_t<1>(p, stream, choice, hd, fgr, fgr_bs, up) : patch_run_t<3>(p, stream, choice, hd, fgr, fgr_bs, up);
+}
+
+// ---- the patch conv with an upsampled source for its leading channels (include/otvm_hip.h)
+extern "C" int otvm_conv2d_accepts_upsampled_input(const otvm_conv_params* p, const otvm_conv_up_params* u) {
+    constexpr int T_PATCH_ID = 14;                                    // T_PATCH of conv_f16x3_kernel.h: tune = (id + 1) * 16 + 1
+    if (!p || !u || !otvm_prec_is_split(p->precision) || !p->w_scale) return 0;
+    if (patch_choice(p) != 1 || p->dil != 1) return 0;               // the 64- and 32-filter tiles; not the 256-filter wide tile
+    if (p->in_res || p->in_scale || p->in_shift || p->in_relu) return 0;
+    if (p->tune && p->tune / 16 - 1 != T_PATCH_ID) return 0;
+    if (p->precision == OTVM_PREC_F16X3 && p->Cout > 32 && !patch_m16()) return 0;
+    if (!u->src || u->Hi < 1 || u->Wi < 1 || u->Cu < CB || u->Cu % CB != 0 || u->Cu > p->Cin) return 0;
+    if (p->H != 2 * u->Hi || p->W != 2 * u->Wi || p->Ho != p->H || p->Wo != p->W) return 0;
+    if (u->src_ld < u->Cu || (u->src_ld & 3) || ((uintptr_t)u->src & 15)) return 0;
+    if (!u->scale != !u->shift || ((uintptr_t)u->scale & 15) || ((uintptr_t)u->shift & 15)) return 0;
+    if (u->act != OTVM_ACT_NONE && u->act != OTVM_ACT_RELU && u->act != OTVM_ACT_LEAKY) return 0;
+    if (u->Cu < p->Cin && (!p->in || (p->in_ld & 3) || ((uintptr_t)p->in & 15) || p->in_ld < p->Cin - u->Cu)) return 0;
+    if (p->batch > 1 && ((u->src_bs & 3) || (u->norm_bs & 3) || (p->in_bs & 3))) return 0;
+    if ((int64_t)u->Hi * u->Wi * u->src_ld * 4 >= 0xFFFFFFF0ll || (int64_t)p->H * p->W * p->in_ld * 4 >= 0xFFFFFFF0ll) return 0;
+    if (u->tile_rows != 0 && !(u->tile_rows == 16 && p->Cout <= 32)) return 0;
+    return 1;
+}
+
+extern "C" int otvm_conv2d_up(const otvm_conv_params* p, const otvm_conv_up_params* u, void* stream) {
+    OTVM_REQUIRE(p && u, "otvm_conv2d_up: null pointer");
+    OTVM_REQUIRE(otvm_conv2d_accepts_upsampled_input(p, u),
+                 "otvm_conv2d_up: not a layer / source the patch kernel takes (otvm_conv2d_accepts_upsampled_input)");
+    OTVM_REQUIRE(p->out && p->w_frag, "otvm_conv2d_up: null pointer");
+    OTVM_REQUIRE(!p->gn_stats || (p->Cout == 64 && p->act == OTVM_ACT_NONE && !p->residual),
+                 "otvm_conv2d_up: fused GroupNorm statistics need Cout = 64, no activation, no residual");
+    OTVM_REQUIRE(!p->gn_scale_out || (p->gn_stats && p->gn_shift_out && p->gn_gamma && p->gn_beta && p->gn_counter),
+                 "otvm_conv2d_up: gn_scale_out needs gn_stats, gn_shift_out, gn_gamma, gn_beta and gn_counter");
+    return patch_run(p, stream, 1, nullptr, nullptr, 0, u);
 }

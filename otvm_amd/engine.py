@@ -68,6 +68,11 @@ FUSE_STM_BLOCK = os.environ.get("OTVM_FUSE_STM_BLOCK", "1") != "0"
 # OTVM_FUSE_STM_BLOCK128: 0 = never, 1 = timed (default), 2 = always (tile from the map size)
 FUSE_STM_BLOCK128 = int(os.environ.get("OTVM_FUSE_STM_BLOCK128", "1"))
 STM128_TILE = int(os.environ.get("OTVM_STM128_TILE", "0"))       # (experiments, with OTVM_FUSE_STM_BLOCK128=2: force pixel tile 1 / 2 / 3)
+# The decoder's 2x upsampled maps (u2 -> U3[:, 0:256], u3 -> D80[:, 0:64]) read at source resolution by the patch convs that
+# consume them (otvm_conv2d_up: the interpolation happens while the conv stages its patch, the 4x copy is never written).  Bit for
+# bit the result of the pass + conv route, so the choice is free to be TIMED at plan time per map (FramePlan._resolve_upfold;
+# cached with the conv tuner's choices).  OTVM_FOLD_UPSAMPLE: 0 = never, 1 = timed (default), 2 = always (where the library takes it)
+FOLD_UPSAMPLE = int(os.environ.get("OTVM_FOLD_UPSAMPLE", "1"))
 FUSE_PPM_HEAD = os.environ.get("OTVM_PPM_HEAD", "1") != "0"
 # round 4 (ABI 17): the GroupNorm statistics of conv3's OUTPUT in the FBA bottlenecks predicted from its input (channel sums +
 # Gram matrix, csrc/gram.hip), so conv3's epilogue normalises, adds the identity, applies the ReLU and writes the block output:
@@ -1206,6 +1211,8 @@ class FramePlan:
         self._n_conv = {}
         self._retired_graphs = []
         self._stm128 = []                                     # launch lists holding an unresolved planes-128 STM block
+        self._upfold = []                                     # upsampled maps whose reader convs may read the source instead (_resolve_upfold)
+        self.upfold_routes = {}                               # GroupNorm name of the map -> 1 folded / 0 pass (reports, tests)
         self._fused_stats = []
         self._convs = []
         self._predicted = []                                  # (layer, otvm_gram_params, slot in self.diag) of every predicted tail
@@ -1329,6 +1336,7 @@ class FramePlan:
     def autotune(self):
         if not (AUTOTUNE and self.e.precision == L.PREC_F16X3):
             self._resolve_stm128(timed=False)
+            self._resolve_upfold(timed=False)
             return
         # realistic operand values while timing (zero-filled operands run the matrix cores at an unrepresentative power)
         filled = []
@@ -1355,6 +1363,8 @@ class FramePlan:
         self._resolve_stm128(timed=FUSE_STM_BLOCK128 == 1)
         torch.cuda.synchronize(self.dev)
         del self._convs[n0:], self._keep[k0:]                  # scratch-bound parameter blocks: not kept
+        self._resolve_upfold(timed=FOLD_UPSAMPLE == 1)
+        torch.cuda.synchronize(self.dev)
         for t in filled:
             t.zero_()
         self.stats.zero_()
@@ -1390,9 +1400,12 @@ class FramePlan:
         return [t[b * n:(b + 1) * n] for b in range(self.B)]
 
     # ---- step builders (S = list being filled)
-    def conv(self, S, x, wname, out, stride=1, pad=0, dil=1, act=NONE, in_relu=0, residual=None, in_norm=None, in_res=None):
+    def conv(self, S, x, wname, out, stride=1, pad=0, dil=1, act=NONE, in_relu=0, residual=None, in_norm=None, in_res=None,
+             up_source=None):
         """in_res (with in_norm): x' = in_act(x * scale + shift + in_res) -- the identity of a residual block whose last apply
-        pass is skipped (otvm_conv_params.in_res; 3x3 patch-kernel layers only)."""
+        pass is skipped (otvm_conv_params.in_res; 3x3 patch-kernel layers only).
+        up_source: the record gn_then_upsample returned for the map that fills the LEADING channels of x (or None): this conv is
+        one of that map's readers and may be switched to otvm_conv2d_up by _resolve_upfold."""
         w = self.e.W[wname]
         assert x.C == w.I_pad, (wname, x.C, w.I_pad)
         Ho = (x.H + 2 * pad - dil * (w.kh - 1) - 1) // stride + 1
@@ -1409,6 +1422,9 @@ class FramePlan:
         abytes = 4 * (x.B * x.H * x.W * w.I * (2 if in_res is not None else 1) + w.O * w.I * w.kh * w.kw
                       + x.B * Ho * Wo * w.O * (2 if residual is not None else 1))
         S.append((self.lib.otvm_conv2d, (C.byref(p),), "conv " + wname, flops, abytes, (x, out.ch(0, _rup(w.O, 4)) if out.C >= _rup(w.O, 4) else out)))
+        if up_source is not None:
+            assert up_source["out"].t is x.t and up_source["out"].off == x.off and stride == 1 and in_norm is None and in_res is None
+            up_source["readers"].append((S, S[-1], p, x, wname))
         return p
 
     def conv_head(self, S, x, wname, hid_out, head_w, head_b, n_out, img, alpha, alpha_stride, alpha_bs, tri=None, sm=None,
@@ -1543,9 +1559,86 @@ class FramePlan:
         if FUSE_GN_APPLY and FUSE_GN_STATS and producer_p is not None:
             sc, sh, nbs = self.gn_table_step(S, x, gn_name, producer_p)
             self.upsample(S, x, out, norm=(sc, sh, gn_act, nbs))
-        else:
-            self.gn(S, x, gn_name, gn_act, conv_p=producer_p)
-            self.upsample(S, x, out)
+            # (returned for conv(up_source=...): the readers of `out` may take x and the table instead of the upsampled copy)
+            m = {"name": gn_name, "S": S, "step": S[-1], "src": x, "norm": (sc, sh, gn_act, nbs), "out": out, "readers": []}
+            self._upfold.append(m)
+            return m
+        self.gn(S, x, gn_name, gn_act, conv_p=producer_p)
+        self.upsample(S, x, out)
+        return None
+
+    def _resolve_upfold(self, timed):
+        """Every 2x upsampled map whose readers were declared (conv(up_source=...)): either the pass + the readers on otvm_conv2d,
+        or no pass and the readers on otvm_conv2d_up -- the same bits either way.  FOLD_UPSAMPLE = 1: whichever is faster on this
+        map, timed once per (map, batch) with both routes warm, the minimum of several alternating repetitions (the buffers hold
+        random values: autotune), cached beside the conv tuner's choices; 2: folded wherever the library takes every reader; 0, or
+        the training forward (its decoder tensors are read back: keep_hid_d): the pass."""
+        stream = torch.cuda.current_stream(self.dev).cuda_stream
+        timed_any = False
+        for m in self._upfold:
+            self.upfold_routes[m["name"]] = 0
+            if FOLD_UPSAMPLE <= 0 or self.e.keep_hid_d or not m["readers"]:
+                continue
+            src, (sc, sh, act, nbs) = m["src"], m["norm"]
+            folded = []
+            for S, step, p, x, wname in m["readers"]:
+                pf, u = L.ConvParams(), L.ConvUpParams()
+                C.memmove(C.byref(pf), C.byref(p), C.sizeof(L.ConvParams))      # (after _bind_stats and tune_convs: statistics, table, tune)
+                pf.inp = x.ch(src.C, x.C - src.C).ptr
+                u.src, u.Hi, u.Wi, u.Cu, u.src_ld, u.src_bs = src.ptr, src.H, src.W, src.C, src.ld, src.bs
+                u.scale, u.shift, u.act, u.norm_bs = sc, sh, act, nbs
+                if not self.lib.otvm_conv2d_accepts_upsampled_input(C.byref(pf), C.byref(u)):
+                    folded = None
+                    break
+                self._keep += [pf, u]
+                w = self.e.W[wname]
+                saved = 4 * x.B * x.P * min(src.C, w.I) * 3 // 4               # the upsampled channels are read at a quarter of the pixels
+                folded.append((self.lib.otvm_conv2d_up, (C.byref(pf), C.byref(u)), step[2] + " (+ up2x)", step[3], step[4] - saved, step[5]))
+            if folded is None:
+                continue
+            key = (-2, src.H, src.W, max(1, src.B), src.C, src.ld) + tuple(v for r in m["readers"] for v in (r[2].Cin, r[2].Cout, r[2].act))
+            if FOLD_UPSAMPLE >= 2:
+                choice = 1
+            elif key in _TUNE_CACHE:
+                choice = _TUNE_CACHE[key]
+            elif not timed:
+                choice = 0
+            else:
+                routes = {0: [m["step"]] + [r[1] for r in m["readers"]], 1: folded}
+
+                def run(c, reps):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(reps):
+                        for st in routes[c]:
+                            L.check(st[0](*st[1], stream), st[2])
+                    e1.record()
+                    return e0, e1, reps
+                self.e.conv_calls += 2 * (2 + 4 * 3) * len(folded)              # (counted like the conv tuner's launches)
+                run(0, 2)
+                run(1, 2)
+                timed_ = [(c,) + run(c, 3) for c in (0, 1, 0, 1, 0, 1, 0, 1)]
+                torch.cuda.synchronize(self.dev)
+                ms = {}
+                for c, e0, e1, r in timed_:
+                    t = e0.elapsed_time(e1) / r
+                    ms[c] = min(ms.get(c, t), t)
+                choice = min(ms, key=ms.get)
+                _TUNE_CACHE[key] = choice
+                TUNE_LOG.append((m["name"] + " (2x upsampling: 0 = pass + reader convs, 1 = read at source resolution by the convs)",
+                                 (2 * src.H, 2 * src.W, src.C, src.ld, src.C, m["out"].ld, 1, 1, 1, 0, 1), choice, ms))   # (a layer-like signature: reports)
+                timed_any = True
+            if choice:
+                at = lambda S, st: next(i for i, q in enumerate(S) if q is st)   # noqa: E731 -- (by identity: tuples of ctypes objects)
+                del m["S"][at(m["S"], m["step"])]
+                for (S, step, p, x, wname), fs in zip(m["readers"], folded):
+                    S[at(S, step)] = fs
+                self.upfold_routes[m["name"]] = 1
+                for b in range(max(1, m["out"].B)):                             # nobody writes these channels any more: zeros, not
+                    m["out"].torch(b).zero_()                                   # the timing's leftovers, for the stage diagnostics
+        self._upfold = []
+        if timed_any:
+            _save_tune_file()
 
     def maxpool(self, S, x, out):
         S.append((self.lib.otvm_maxpool3x3s2_b, (x.ptr, x.H, x.W, x.C, x.ld, out.ptr, out.ld, x.B, x.bs, out.bs), "maxpool"))
@@ -1882,12 +1975,14 @@ class FramePlan:
         self.gn_then_upsample(S, u1b, de + "conv_up1.4", LEAKY, cp, self.U2.ch(0, 256))
         u2 = self.buf("u2", H4, W4, 256)
         cp = self.conv(S, self.U2, de + "conv_up2.0", u2, pad=1)
-        self.gn_then_upsample(S, u2, de + "conv_up2.1", LEAKY, cp, self.U3.ch(0, 256))
+        # U3[:, 0:256] and D80[:, 0:64] are written by these two passes only, and read by the convs named as their readers only: where
+        # _resolve_upfold takes the pass out, the channels keep the zeros of the plan's construction
+        up2 = self.gn_then_upsample(S, u2, de + "conv_up2.1", LEAKY, cp, self.U3.ch(0, 256))
         u3 = self.buf("u3", H2, W2, 64)
-        cp = self.conv(S, self.U3, de + "conv_up3.0", u3, pad=1)
-        self.gn_then_upsample(S, u3, de + "conv_up3.1", LEAKY, cp, self.D80.ch(0, 64))
+        cp = self.conv(S, self.U3, de + "conv_up3.0", u3, pad=1, up_source=up2)
+        up3 = self.gn_then_upsample(S, u3, de + "conv_up3.1", LEAKY, cp, self.D80.ch(0, 64))
         h32 = self.buf("h32", Hp, Wp, 32)
-        self.conv(S, self.D80, de + "conv_up4.0", h32, pad=1, act=LEAKY)      # ch 72.. carry zero weights
+        self.conv(S, self.D80, de + "conv_up4.0", h32, pad=1, act=LEAKY, up_source=up3)      # ch 72.. carry zero weights
         img = self.D80.ch(67, 3)
         fuse_head = FUSE_HEAD and e.precision == L.PREC_F16X3 and e.W[de + "conv_up4.2"].w_frag is not None
         if fuse_head:
@@ -1904,7 +1999,7 @@ class FramePlan:
         # ---------------- refinement (FBA/models.py:417-435)
         rf = "NET.refine."
         r0 = self.buf("r0", Hp, Wp, 64)
-        cp = self.conv(S, self.D80, rf + "conv1.0", r0, pad=1)
+        cp = self.conv(S, self.D80, rf + "conv1.0", r0, pad=1, up_source=up3)
         # conv1's GroupNorm + LeakyReLU is read twice, by layer1.conv1 (a patch conv: normalises while staging) and as the
         # residual of layer1.bn2's apply pass (normalises on the fly): the normalised 535 MB tensor is never written
         x, x_norm = r0, None

@@ -34,6 +34,12 @@ class ConvParams(C.Structure):
                 ("in_res", vp), ("in_res_ld", i32), ("in_res_bs", i64)]
 
 
+class ConvUpParams(C.Structure):
+    """otvm_conv_up_params: the upsampled source of otvm_conv2d_up (additive to ABI 21)."""
+    _fields_ = [("src", vp), ("Hi", i32), ("Wi", i32), ("Cu", i32), ("src_ld", i32), ("src_bs", i64),
+                ("scale", vp), ("shift", vp), ("act", i32), ("norm_bs", i32), ("tile_rows", i32)]
+
+
 class StmBottleneckParams(C.Structure):
     _fields_ = [("x", vp), ("H", i32), ("W", i32), ("Cin", i32), ("x_ld", i32), ("y", vp), ("y_ld", i32),
                 ("w1f", vp), ("w2f", vp), ("w3f", vp), ("s1", vp), ("s2", vp), ("s3", vp), ("b1", vp), ("b2", vp), ("b3", vp),
@@ -121,6 +127,8 @@ _PROTOS = {
     "otvm_conv2d_accepts_input_norm": (i32, [C.POINTER(ConvParams)]),
     "otvm_conv2d_input_norm_kind": (i32, [C.POINTER(ConvParams)]),
     "otvm_conv2d_accepts_input_residual": (i32, [C.POINTER(ConvParams)]),
+    "otvm_conv2d_up": (i32, [C.POINTER(ConvParams), C.POINTER(ConvUpParams), vp]),
+    "otvm_conv2d_accepts_upsampled_input": (i32, [C.POINTER(ConvParams), C.POINTER(ConvUpParams)]),
     "otvm_conv2d_head": (i32, [C.POINTER(ConvParams), C.POINTER(HeadParams), vp]),
     "otvm_conv2d_head_fgr": (i32, [C.POINTER(ConvParams), C.POINTER(HeadParams), vp, i64, vp]),
     "otvm_head16_weight_bytes_f16x3": (i64, []),

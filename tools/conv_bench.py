@@ -1,6 +1,12 @@
 """Micro-benchmark of otvm_conv2d on single layer shapes (tuning aid; GPU only).
 
     python tools/conv_bench.py [--prec 1] [--iters 20] [--shape Cin,Cout,k,stride,dil,H,W ...]
+
+--up CU: the leading CU input channels are the 2x upsampling of a half-resolution tensor with a GroupNorm table + LeakyReLU (the
+decoder's u2 / u3): times the upsampling pass + otvm_conv2d against otvm_conv2d_up, which reads the source while staging, e.g.
+    python tools/conv_bench.py --up 64 --bias 1 --shape 80,32,3,1,1,1088,1920 --shape 80,64,3,1,1,1088,1920
+    python tools/conv_bench.py --up 256 --gn 1 --shape 320,64,3,1,1,544,960
+--only pass|conv|fold runs one of the three launches alone (counter passes: one kernel per process).
 """
 import argparse
 import ctypes as C
@@ -38,6 +44,8 @@ def main():
     ap.add_argument("--pad-ld", type=int, default=0, help="extra floats per pixel row of the input / output / residual views (ld = C + pad)")
     ap.add_argument("--zero", type=int, default=0, help="power probe: 1 = all-zero input, 2 = all-zero weights, 3 = both (the matrix cores' "
                                                         "power depends on the operands; times only)")
+    ap.add_argument("--up", type=int, default=0, help="leading channels read from a half-resolution source (otvm_conv2d_up against pass + conv)")
+    ap.add_argument("--only", default=None, choices=["pass", "conv", "fold"], help="with --up: launch only this step")
     ap.add_argument("--tune", default="0", help="otvm_conv_params.tune codes to time, comma separated; 'all' = every candidate")
     args = ap.parse_args()
     shapes = [tuple(int(v) for v in s.split(",")) for s in args.shape] if args.shape else DEFAULT
@@ -69,6 +77,9 @@ def main():
             p.gn_stats = stats.data_ptr()
         ws = torch.empty(16 << 20, device=dev)
         p.splitk_ws, p.splitk_ws_bytes = ws.data_ptr(), ws.numel() * 4
+        if args.up:
+            bench_up(lib, args, st, dev, x, cw, out, p, Cin, Cout, H, W)
+            continue
         if args.tune == "all":
             codes = (C.c_int * 128)()
             n = int(lib.otvm_conv2d_candidates(C.byref(p), codes, 128))
@@ -94,6 +105,53 @@ def main():
             label = "heuristic" if tune == 0 else "%s/S%d" % (names.get(tune // 16 - 1, "?"), tune & 15)
             print("Cin %4d Cout %4d k%d s%d d%d %4dx%-4d %-14s: %7.3f ms  %7.1f TFLOP/s" %
                   (Cin, Cout, k, stride, dil, H, W, label, ms, fl / ms / 1e9))
+
+
+def bench_up(lib, args, st, dev, x, cw, out, p, Cin, Cout, H, W):
+    Cu, Hi, Wi = args.up, H // 2, W // 2
+    assert H == 2 * Hi and W == 2 * Wi and Cu % 16 == 0 and Cu <= Cin
+    src = Act(torch.randn(Hi * Wi * Cu, device=dev), Hi, Wi, Cu)
+    tab = torch.cat([1.0 + 0.1 * torch.randn(Cu, device=dev), 0.1 * torch.randn(Cu, device=dev)])
+    pf, u = L.ConvParams(), L.ConvUpParams()
+    C.memmove(C.byref(pf), C.byref(p), C.sizeof(L.ConvParams))
+    pf.inp = x.ch(Cu, Cin - Cu).ptr
+    u.src, u.Hi, u.Wi, u.Cu, u.src_ld = src.ptr, Hi, Wi, Cu, src.ld
+    u.scale, u.shift, u.act = tab.data_ptr(), tab.data_ptr() + 4 * Cu, 2
+    if not lib.otvm_conv2d_accepts_upsampled_input(C.byref(pf), C.byref(u)):
+        print("Cin %d Cout %d %dx%d: otvm_conv2d_up does not take this layer" % (Cin, Cout, H, W))
+        return
+    up = x.ch(0, Cu)
+
+    def do_pass():
+        L.check(lib.otvm_upsample_bilinear_b(src.ptr, Hi, Wi, Cu, src.ld, u.scale, u.shift, 2, 0, 0, up.ptr, H, W, up.ld, 1, 0, 0, 0, 0, st))
+
+    def do_conv():
+        L.check(lib.otvm_conv2d(C.byref(p), st))
+
+    def do_fold():
+        L.check(lib.otvm_conv2d_up(C.byref(pf), C.byref(u), st))
+    steps = {"pass": do_pass, "conv": do_conv, "fold": do_fold}
+    if args.only:
+        for _ in range(3):
+            steps[args.only]()
+        torch.cuda.synchronize()
+        return
+    ms = {}
+    for rnd_ in range(3):                                   # alternating, the minimum of three rounds
+        for name, fn in steps.items():
+            for _ in range(3):
+                fn()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            t = e0.elapsed_time(e1) / args.iters
+            ms[name] = min(ms.get(name, t), t)
+    print("Cin %4d (%d upsampled) Cout %4d %4dx%-4d: pass %.3f ms + conv %.3f ms = %.3f ms | folded conv %.3f ms (conv alone x %.2f)" %
+          (Cin, Cu, Cout, H, W, ms["pass"], ms["conv"], ms["pass"] + ms["conv"], ms["fold"], ms["fold"] / ms["conv"]))
 
 
 if __name__ == "__main__":
