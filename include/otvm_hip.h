@@ -72,7 +72,9 @@ const char* otvm_last_error(void);
                                   likewise the temporal stabilisation of alpha: otvm_luma_u8 and otvm_temporal_blend with
                                   otvm_temporal_params;
                                   likewise the patch conv with an upsampled source: otvm_conv2d_up and
-                                  otvm_conv2d_accepts_upsampled_input with otvm_conv_up_params) */
+                                  otvm_conv2d_accepts_upsampled_input with otvm_conv_up_params;
+                                  likewise region-of-interest matting: otvm_trimap_bbox, otvm_roi_crop and otvm_roi_paste with
+                                  otvm_roi_bbox_params, otvm_roi_crop_params and otvm_roi_paste_params) */
 int otvm_abi_version(void);
 
 /* ---------------------------------------------------------------- weights (load time) ----------
@@ -679,6 +681,64 @@ typedef struct otvm_temporal_params {
 } otvm_temporal_params;
 int otvm_luma_u8(const uint8_t* img, int H, int W, int u8_rgb, uint8_t* grey, void* stream);
 int otvm_temporal_blend(const otvm_temporal_params* p, void* stream);
+
+/* ---------------------------------------------------------------- region-of-interest matting ----------
+ * Run the network in a window round the subject (an extension; otvm_amd/roi.py, run_video_matte(roi=...)): the boxes of a class
+ * map, the crop of a frame's inputs to a window and the paste of the window's results into the frame.  Checked by definition only:
+ * the result is the matte of the cropped clip pasted back, NOT the full-frame matte.  All three run on the caller's stream, never
+ * synchronise with the host, and launch nothing when an argument is refused (nonzero; otvm_last_error() starts with the function's
+ * name).  Sizes are 1 .. 16383 a side.  New symbols only (additive, as the entries above): the ABI number stays.
+ *
+ * otvm_trimap_bbox: out[0..3] = y0, x0, y1, x1 (inclusive) of the UNKNOWN pixels, out[4..7] the same of the NON-BACKGROUND pixels;
+ * an empty set gives (H, W, -1, -1).  Exactly one source:
+ *   trimap float [3,H,W] (one-hot or probabilities): non-bg iff max(t1, t2) > t0; unknown iff non-bg and t1 >= t2 (a NaN fails the
+ *          comparison it stands in);
+ *   labels uint8 [H,W]: 1 is unknown, 1 or 2 non-bg, every other value (0, 255) neither.
+ * out needs no initialisation: the call first stores the empty boxes, then reduces per wave and workgroup and merges with
+ * integer min / max atomics, which do not depend on the order of arrival -- two calls give equal bits.  out may be slot t of a
+ * [T,8] buffer: only its own 8 words are touched, and a clip is read back with one copy.                                      */
+typedef struct otvm_roi_bbox_params {
+    const float* trimap;            /* [3,H,W] or NULL */
+    const uint8_t* labels;          /* [H,W] or NULL */
+    int H, W;
+    int32_t* out;                   /* 8 words */
+} otvm_roi_bbox_params;
+int otvm_trimap_bbox(const otvm_roi_bbox_params* p, void* stream);
+
+/* otvm_roi_crop: the h x w window at origin (y0, x0) of an H x W frame, one launch, every pair optional (a destination without
+ * its source is refused, and so is a call with no destination): frame uint8 [H,W,3] -> [h,w,3], trimap float [3,H,W] -> [3,h,w],
+ * labels uint8 [H,W] -> [h,w].  Pure copies; nothing is assumed about the alignment of a window row (any x0, any W).        */
+typedef struct otvm_roi_crop_params {
+    int H, W, y0, x0, h, w;         /* 0 <= y0, y0 + h <= H, 0 <= x0, x0 + w <= W */
+    const uint8_t* frame;    uint8_t* frame_out;
+    const float* trimap;     float* trimap_out;
+    const uint8_t* labels;   uint8_t* labels_out;
+} otvm_roi_crop_params;
+int otvm_roi_crop(const otvm_roi_crop_params* p, void* stream);
+
+/* otvm_roi_paste: a window's results back at H x W in one pass; every output is optional (at least one), every element of a
+ * requested output is written.  fp32, one IEEE operation per step, no atomics (two calls give equal bits).
+ *   inside the window : alpha, trimap and fgr are the window's values, unchanged;
+ *                       alpha_u8 = (uint8) min(max(trunc(a * 255.f), 0), 255), the byte otvm_crop_outputs writes; a non-finite
+ *                       alpha gives byte 0, as in otvm_fgr_outputs;
+ *   outside           : trimap = `outside` at that pixel, or (1, 0, 0) when outside is NULL; alpha = 1.f where outside's fg plane
+ *                       is 1.f, else 0.f (byte 255 / 0); fgr = (float)byte * (1.f / 255.f) of the frame's pixel, stored R, G, B
+ *                       (u8_rgb says which byte is R, as otvm_preprocess_params.u8_rgb does).
+ * fgr needs win_fgr and frame.  RGBA / composite bytes: otvm_fgr_outputs on the pasted planes with Hp = H, Wp = W.           */
+typedef struct otvm_roi_paste_params {
+    int H, W, y0, x0, h, w;         /* as otvm_roi_crop_params */
+    const float* win_alpha;         /* [h,w] */
+    const float* win_trimap;        /* [3,h,w] */
+    const float* win_fgr;           /* [3,h,w] R, G, B, or NULL */
+    const uint8_t* frame;           /* [H,W,3], or NULL without fgr */
+    int u8_rgb;
+    const float* outside;           /* one-hot [3,H,W] or NULL: everything outside the window is background */
+    float* alpha;                   /* [H,W] */
+    uint8_t* alpha_u8;              /* [H,W] */
+    float* trimap;                  /* [3,H,W] */
+    float* fgr;                     /* [3,H,W] R, G, B */
+} otvm_roi_paste_params;
+int otvm_roi_paste(const otvm_roi_paste_params* p, void* stream);
 
 /* ---------------------------------------------------------------- range guard / clear -----------
  * f16x3 splits fp32 operands into fp16 halves: |x| >= 65504 loses accuracy, >= 131008 becomes inf.

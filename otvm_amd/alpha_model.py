@@ -94,6 +94,12 @@ class EvalModel(nn.Module):
         if self._engine is not None:
             self._engine.drop_non_anchors()
 
+    def drop_plans(self):
+        """Forget every frame plan of the engine, with its buffers and the memory bank (a process that mattes clips of many sizes
+        -- a region-of-interest window per clip -- calls this BETWEEN clips; the next frame plans again)."""
+        if self._engine is not None:
+            self._engine._drop_plans()
+
     @torch.no_grad()
     def forward(self, a, fg, bg, tri=None, tri_gt=None, first_frame=False, last_frame=False, memorize=False,
                 max_memory_num=2, large_input=False, keyframe=False, labels=None, _frame_id=None, _cls_override=None,

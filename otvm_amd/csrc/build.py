@@ -33,6 +33,7 @@ SOURCES = [
     ("edt.hip", ["-ffp-contract=off"]),
     ("mask_trimap.hip", ["-ffp-contract=off"]),
     ("temporal.hip", ["-ffp-contract=off"]),
+    ("roi.hip", ["-ffp-contract=off"]),
     ("memory_read.hip", []),
     ("memory_read_f16x3.hip", []),
     ("metrics.hip", []),

@@ -37,6 +37,15 @@ and the change of alpha at which it lets go, --stabilise-region unknown|all wher
 checkpoint here, the filter is checked by definition and by property on synthetic clips, not by quality on real footage.  Works
 with --masks, --keyframes (forward-only schedules), --work-scale, --fgr and --composite; refused with --viz, --batch > 1 and
 without --demo.  The summary carries stabilise.
+--roi auto|Y0,X0,H,W [--roi-margin M] (demo layout): region-of-interest matting -- the network runs in a window round the subject
+and alpha (with --fgr / --composite also the foreground) is pasted back into the frame (video.run_video_matte(roi=...),
+otvm_amd/roi.py).  auto with --masks frame tracks the mask's unknown band frame by frame; auto otherwise places ONE window round
+the classes other than background of the clip's trimaps / masks / label maps, which the subject must not leave (roi_clipped in the
+summary lists the frames whose propagated trimap reaches a side of the window).  The result is the matte of the cropped clip, NOT
+the full-frame matte (the network's global context is the window's), it is checked by definition only, and the default margin
+(32) is a PLACEHOLDER.  Works with --masks, --keyframes, --fgr, --composite and --stabilise; refused with --work-scale, --viz,
+--batch > 1 and without --demo.  The summary carries roi, roi_margin and per clip roi_size and roi_clipped.  Between clips whose
+window size differs the engine's frame plans are dropped (nothing else evicts them).
 Frame IO runs through otvm_amd/io_pipeline.py: the demo flow decodes ahead in a thread pool and uploads on a copy
 stream, both flows download the 8-bit alphas asynchronously and PNG-encode them in a pool (the reference's loop blocks
 on .cpu() + cv2.imwrite per frame, eval.py:209-217).
@@ -112,6 +121,22 @@ def parse_stabilise_options(strength, taus, region):
     return kw
 
 
+def parse_roi_options(roi, margin):
+    """--roi "auto" | "Y0,X0,H,W", --roi-margin M -> run_video_matte's (roi, roi_margin); (None, 32) when --roi was not given."""
+    if roi is None:
+        if margin is not None:
+            raise SystemExit("eval_cli: --roi-margin belongs to --roi")
+        return None, 32
+    if margin is not None and margin < 0:
+        raise SystemExit("eval_cli: --roi-margin is a number of pixels >= 0, got %d" % margin)
+    if roi != "auto":
+        parts = roi.split(",")
+        if len(parts) != 4 or not all(x.strip().isdigit() for x in parts) or int(parts[2]) < 1 or int(parts[3]) < 1:
+            raise SystemExit("eval_cli: --roi is auto or a window Y0,X0,H,W (pixels, H and W at least 1), got %r" % roi)
+        roi = tuple(int(x) for x in parts)
+    return roi, 32 if margin is None else margin
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--data", required=True)
@@ -143,6 +168,11 @@ def main(argv=None):
                          "(default 24,0.5: placeholders)")
     ap.add_argument("--stabilise-region", default=None, choices=["unknown", "all"],
                     help="--stabilise: filter only the trimap's unknown class (default) or every pixel")
+    ap.add_argument("--roi", default=None, metavar="auto|Y0,X0,H,W",
+                    help="demo layout: run the network in a window round the subject and paste the result back (the matte of the "
+                         "cropped clip, not the full-frame matte); auto places the window from the trimaps / masks")
+    ap.add_argument("--roi-margin", type=int, default=None, metavar="M",
+                    help="--roi auto: pixels kept round the subject's box (default 32: a placeholder, not tuned on real footage)")
     ap.add_argument("--max-frames", type=int, default=None, help="only the first N frames of every sequence")
     ap.add_argument("--weights", default=None)
     ap.add_argument("--synthetic-weights", action="store_true")
@@ -182,6 +212,18 @@ def main(argv=None):
     if stabilise is not None and args.viz:
         raise SystemExit("eval_cli: --stabilise changes alpha behind the frame; the --viz panels show the network's own outputs: "
                          "drop one of them")
+    roi, roi_margin = parse_roi_options(args.roi, args.roi_margin)
+    if roi is not None and not args.demo:
+        raise SystemExit("eval_cli: --roi belongs to the demo routes (the window is placed round a trimap's classes; the "
+                         "VideoMatting108 flow derives its trimap from the ground truth); add --demo")
+    if roi is not None and args.batch is not None and args.batch > 1:
+        raise SystemExit("eval_cli: --batch %d steps clips in lock-step through matte_batch, which does not implement --roi"
+                         % args.batch)
+    if roi is not None and args.viz:
+        raise SystemExit("eval_cli: --roi pastes alpha into the frame behind the network; the --viz panels show the network's own "
+                         "outputs, at the window's size: drop one of them")
+    if roi is not None and args.work_scale is not None:
+        raise SystemExit("eval_cli: --roi and --work-scale exclude each other (a window at the working resolution is out of scope)")
     if args.masks and not args.demo:
         raise SystemExit("eval_cli: --masks reads the demo layout's mask/ folder; add --demo")
     if args.masks and args.batch is not None and args.batch > 1:
@@ -248,7 +290,8 @@ def main(argv=None):
         # (--viz and --sync-io are single-clip features -- matte_batch writes no viz frames and decodes every clip of a group up
         #  front -- so they keep batch 1 unless --batch is given explicitly)
         if world > 1 and any(k is not None for k in keys) and not (args.viz or args.sync_io or args.fgr or args.composite
-                                                                   or args.keyframes or args.masks or stabilise is not None):
+                                                                   or args.keyframes or args.masks or stabilise is not None
+                                                                   or roi is not None):
             def padded(k):
                 lw, uw, lh, uh = pad_amounts(k[0], k[1], 32)
                 return (k[0] + lh + uh) * (k[1] + lw + uw)
@@ -285,6 +328,8 @@ def main(argv=None):
             torch.cuda.synchronize(dev)
         share_tune_cache(0)
 
+    roi_state = {"size": None}                        # --roi: the window size of the previous clip
+
     def matte(seq):
         demo = seq["item"][0] == "demo"
         keyed = demo and (args.keyframes or args.masks == "key")   # frames in schedule order: decoded up front, not prefetched
@@ -303,7 +348,8 @@ def main(argv=None):
         cwriter = AlphaWriter(dev, os.path.join(args.out, "comp", seq["name"]), png_names) if args.composite is not None else None
         eng_of = model.module
         # --work-scale and --stabilise remake the foreground bytes behind the engine: they arrive through on_foreground
-        late_bytes = args.work_scale is not None or stabilise is not None
+        # (--roi: the engine's are at the window's size; the full-resolution ones likewise)
+        late_bytes = args.work_scale is not None or stabilise is not None or roi is not None
         bgr = not (demo and not args.sync_io and not keyed)   # the prefetcher hands out RGB frames, the decoded arrays are BGR
 
         def new_background():
@@ -371,7 +417,7 @@ def main(argv=None):
                                   max_num=args.max_num, masks=per_frame,
                                   on_frame=save, device=dev, frames_are_rgb=rgb, keep_on_device=True,
                                   foreground=want_fgr, new_background=new_background(), keyframes=kf,
-                                  stabilise=stabilise,
+                                  stabilise=stabilise, **(dict(roi=roi, roi_margin=roi_margin) if roi is not None else {}),
                                   **(dict(on_foreground=save_full if want_fgr else None) if late_bytes else {}),
                                   **(dict(work_scale=args.work_scale, work_radius=args.work_radius, work_eps=args.work_eps)
                                      if args.work_scale is not None else {}))
@@ -379,6 +425,14 @@ def main(argv=None):
                 pre.close()
             if args.work_scale is not None:
                 res["work_scale"], res["work_size"] = args.work_scale, list(res["work_size"] or ())
+            if roi is not None:
+                res["roi"] = [list(w) for w in res["roi"]]
+                res["roi_size"] = list(res["roi_size"] or ())
+                # every window size is a frame plan of its own and nothing else evicts them: when this clip's size differs from
+                # the previous clip's, the engine's plans are dropped before the next clip (it plans again at its own size)
+                if roi_state["size"] is not None and res["roi_size"] and roi_state["size"] != res["roi_size"]:
+                    model.module.drop_plans()
+                roi_state["size"] = res["roi_size"] or roi_state["size"]
         else:
             res = run_video_matte(model, data["frames"], alphas=data["alphas"], backgrounds=data["backgrounds"],
                                   skip=args.skip, max_num=args.max_num, on_frame=save, device=dev,
@@ -431,6 +485,10 @@ def main(argv=None):
         summary["masks"] = args.masks
         summary["mask_band"] = list(mask_band) if isinstance(mask_band, tuple) else [dk if mask_band is None else mask_band] * 2
         summary["mask_thresholds"] = [mask_lo, mask_hi]
+    if roi is not None:
+        summary["roi"], summary["roi_margin"] = (roi if roi == "auto" else list(roi)), roi_margin
+        summary["roi_size"] = {seqs[i]["name"]: o["roi_size"] for i, o in summary["outputs"].items() if o.get("roi_size")}
+        summary["roi_clipped"] = {seqs[i]["name"]: o["roi_clipped"] for i, o in summary["outputs"].items() if "roi_clipped" in o}
     if stabilise is not None:
         summary["stabilise"] = {k: stabilise.get(k, d) for k, d in (("strength", 0.5), ("tau_colour", 24.0), ("tau_alpha", 0.5),
                                                                       ("region", "unknown"))}

@@ -104,6 +104,21 @@ class TemporalParams(C.Structure):
                 ("out", vp), ("out_u8", vp)]
 
 
+class RoiBboxParams(C.Structure):
+    _fields_ = [("trimap", vp), ("labels", vp), ("H", i32), ("W", i32), ("out", vp)]
+
+
+class RoiCropParams(C.Structure):
+    _fields_ = [("H", i32), ("W", i32), ("y0", i32), ("x0", i32), ("h", i32), ("w", i32),
+                ("frame", vp), ("frame_out", vp), ("trimap", vp), ("trimap_out", vp), ("labels", vp), ("labels_out", vp)]
+
+
+class RoiPasteParams(C.Structure):
+    _fields_ = [("H", i32), ("W", i32), ("y0", i32), ("x0", i32), ("h", i32), ("w", i32),
+                ("win_alpha", vp), ("win_trimap", vp), ("win_fgr", vp), ("frame", vp), ("u8_rgb", i32), ("outside", vp),
+                ("alpha", vp), ("alpha_u8", vp), ("trimap", vp), ("fgr", vp)]
+
+
 class PpmHeadParams(C.Structure):
     _fields_ = [("pooled", vp), ("C", i32), ("K_pad", i32), ("Cout", i32),
                 ("w", vp * 4), ("bias", vp * 4), ("gamma", vp * 4), ("beta", vp * 4), ("out", vp * 4),
@@ -181,6 +196,9 @@ _PROTOS = {
     "otvm_matting_messddt": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
     "otvm_luma_u8": (i32, [vp, i32, i32, i32, vp, vp]),
     "otvm_temporal_blend": (i32, [C.POINTER(TemporalParams), vp]),
+    "otvm_trimap_bbox": (i32, [C.POINTER(RoiBboxParams), vp]),
+    "otvm_roi_crop": (i32, [C.POINTER(RoiCropParams), vp]),
+    "otvm_roi_paste": (i32, [C.POINTER(RoiPasteParams), vp]),
     "otvm_gn_stats_b": (i32, [vp, i64, i32, i32, vp, i32, i64, i32, vp]),
     "otvm_gn_table_b": (i32, [vp, i64, i32, vp, vp, vp, vp, i32, i32, i32, vp]),
     "otvm_gn_apply_b": (i32, [C.POINTER(GnApplyParams), vp]),

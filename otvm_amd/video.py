@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import guided, temporal
+from . import roi as _roi
 from .alpha_model import background_colour
 from .masks import Mask, as_mask
 
@@ -142,7 +143,11 @@ class _ClipPlan:
     The model is only asked for the band of a Mask that names none."""
 
     def __init__(self, model, frames, trimap, alphas, keyframes, mask, masks, backgrounds, work_scale, work_radius, work_eps, skip,
-                 max_num):
+                 max_num, roi=None, roi_margin=32):
+        self.roi, self.region = None, None                # the checked (window or "auto", margin); run_video_matte's _RegionOfInterest
+        if roi is not None:
+            # (host only, like everything here: the window itself is placed by upload(), which has the sources on the device)
+            self.roi = _RegionOfInterest.refuse(roi, roi_margin, frames, alphas, backgrounds, work_scale)
         if work_scale is not None:
             if work_scale not in guided.SCALES:
                 raise ValueError("run_video_matte: work_scale is 2, 3 or 4 (an integer scale), got %r" % (work_scale,))
@@ -203,6 +208,10 @@ class _ClipPlan:
         self.steps, self.kinds, self.k0, self.natural = [], {}, 0, True
         self.tri, self.lab, self.ones = {}, {}, None
         self.mask_hw = {}                                 # frame -> the size of the mask it was given (checked against the frame)
+        self.T, self.skip, self.max_num = T, skip, max_num
+        if self.roi is not None and self.sources is None:
+            raise ValueError("run_video_matte: roi belongs to the trimap flow (`trimap`, `mask`, `keyframes` or `masks`): the window "
+                             "is placed round the trimaps' classes")
         if T == 0:
             return
         for t, v in (self.sources or {}).items():
@@ -222,11 +231,17 @@ class _ClipPlan:
             h, w = np.shape(keyframes[self.k0])[-2:]
             if work_scale is not None:
                 h, w = guided.work_size(h, w, work_scale)
-            large = memory_schedule(0, h, w, skip, max_num)[2]
-            self.steps = keyframe_schedule(T, self.kinds, int(skip * 2) if large else skip)
+            if self.roi is not None and self.roi[0] != "auto":
+                h, w = self.roi[0][2:]                    # (roi="auto": upload() places the window and schedules again)
+            self._schedule(h, w)
         else:
             self.steps = [(i, "frame", i == 0, i == T - 1, None) for i in range(T)]  # alpha flow: eval.py's loop as it is
         self.natural = all(st[0] == j for j, st in enumerate(self.steps))
+
+    def _schedule(self, h, w):
+        """The keyframe steps of a clip the model runs at h x w (the large-input rule doubles the effective skip)."""
+        large = memory_schedule(0, h, w, self.skip, self.max_num)[2]
+        self.steps = keyframe_schedule(self.T, self.kinds, int(self.skip * 2) if large else self.skip)
 
     def _trimap(self, v, dev):
         """One source of kind "key" as the model takes it: [1,1,3,h,w] on the device, reduced to the working resolution."""
@@ -240,10 +255,16 @@ class _ClipPlan:
     def upload(self, dev):
         """The part that needs the device, once per clip at the resolution given: the user trimap (25 MB as fp32 at 1080p) is
         uploaded once, not once per frame.  (``masks`` converts per frame: inputs().)"""
-        if self.per_frame or self.sources is None or not self.steps:
+        if self.sources is None or not self.steps:
+            return
+        if self.per_frame:
+            if self.region is not None:
+                self._track(dev)
             return
         # masks become ordinary trimaps / label maps here, all of them before anything is reduced
         plain = {t: v.convert(self.model, dev) if isinstance(v, Mask) else v for t, v in self.sources.items()}
+        if self.region is not None:
+            plain = self._window(plain, dev)
         for t, v in plain.items():
             if self.kinds[t] == "key":
                 self.tri[t] = self._trimap(v, dev)
@@ -251,6 +272,35 @@ class _ClipPlan:
                 self.lab[t] = _as_tensor(v).to(dev)
                 if self.work_scale is not None:
                     self.lab[t] = guided.downsample_labels(self.lab[t], self.work_scale)
+
+    def _track(self, dev):
+        """``masks`` with ``roi``: the pre-pass.  Every mask is converted and the box of its unknown band taken -- T box calls into
+        one [T,8] buffer, ONE read-back -- and the region places a window per frame.  No trimap is kept: inputs() converts again."""
+        if len(set(self.mask_hw.values())) != 1:
+            raise ValueError("run_video_matte: roi needs masks of one resolution, got %s" % sorted(set(self.mask_hw.values())))
+        (H, W), = set(self.mask_hw.values())
+        rows = torch.empty((self.T, 8), dtype=torch.int32, device=dev)
+        for t in range(self.T):
+            _roi.trimap_bbox(self.sources[t].convert(self.model, dev), rows[t])
+        self.region.place_tracking(_roi.boxes_of(rows)[0], H, W)
+
+    def _window(self, plain, dev):
+        """``roi`` with sources that serve the whole clip: the region places ONE window from the union of their non-background
+        boxes (label maps count with their labels 1 and 2; one [n,8] buffer, one read-back) and every source is cropped to it, once."""
+        order = sorted(plain)
+        on_dev = {t: _as_tensor(plain[t]).to(dev) for t in order}
+        on_dev = {t: v.float() if self.kinds[t] == "key" else v for t, v in on_dev.items()}
+        sizes = {tuple(v.shape[-2:]) for v in on_dev.values()}
+        if len(sizes) != 1:
+            raise ValueError("run_video_matte: roi needs trimaps / label maps of one resolution, got %s" % sorted(sizes))
+        (H, W), = sizes
+        rows = torch.empty((len(order), 8), dtype=torch.int32, device=dev)
+        for j, t in enumerate(order):
+            _roi.trimap_bbox(on_dev[t], rows[j])
+        self.region.place_static(dict(zip(order, _roi.boxes_of(rows)[1])), H, W, self.T)
+        win = self.region.window(0)
+        self._schedule(win[2], win[3])
+        return {t: (_roi.crop(win, trimap=v)[1] if self.kinds[t] == "key" else _roi.crop(win, labels=v)[2]) for t, v in on_dev.items()}
 
     def check_masks(self, i, full_hw):
         """The one refusal of the masks that needs a frame: masks of a keyframe clip are all held against the first frame that
@@ -266,6 +316,8 @@ class _ClipPlan:
         if self.sources is None:
             return _as_tensor(self.alphas[i]).to(dev).float()[None, None, None], None, {}
         self.ones = _ones_alpha(self.ones, H, W, dev)
+        if self.per_frame and self.region is not None:
+            return self.ones, self.region.take_trimap()[None, None], {}   # (cropped with the frame, in stage()'s one launch)
         if self.per_frame:
             return self.ones, self._trimap(self.sources[i], dev), {}     # this frame's own trimap; nothing is kept of it
         more = {}
@@ -352,6 +404,158 @@ class _WorkingResolution:
         return self.ups.foreground_bytes(alpha, self.fgr_full, self.rgb, nb)
 
 
+class _RegionOfInterest:
+    """``roi``'s side of a frame step: stage() crops the frame (with ``masks`` also the frame's trimap, in the same launch) to the
+    frame's window, finish() pastes the window's alpha, trimap (and F) back into H x W.  refuse() is the host-only part, before
+    anything is uploaded; the windows are placed by _ClipPlan.upload(), which holds the sources:
+      place_tracking : ``masks``: one size for the clip (one engine plan), an origin per frame from the frame's unknown box;
+                       outside the window alpha follows the frame's own trimap
+      place_static   : every other route: one window for the clip; outside it is background, and nothing there is looked at"""
+
+    def __init__(self, plan, foreground, frames_are_rgb, new_background):
+        self.spec, self.margin = plan.roi
+        self.plan, self.foreground, self.rgb = plan, foreground, bool(frames_are_rgb)
+        self.new_background, self.bg_cache = new_background, {}
+        self.windows, self.HW, self.tracking = None, None, False
+        self.full = self.outside = self.tri = self.fgr_full = None
+        self.rows, self.seen = None, []                   # static: [T,8] boxes of the output trimaps, in window coordinates
+
+    @staticmethod
+    def refuse(spec, margin, frames, alphas, backgrounds, work_scale):
+        """-> (the window as four ints or "auto", the margin)"""
+        if isinstance(spec, str):
+            if spec != "auto":
+                raise ValueError("run_video_matte: roi is None, 'auto' or a window (y0, x0, h, w), got %r" % (spec,))
+        else:
+            try:
+                ok = len(spec) == 4 and all(not isinstance(v, bool) and int(v) == v for v in spec)
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError("run_video_matte: roi is None, 'auto' or a window (y0, x0, h, w) of four integers, got %r" % (spec,))
+            spec = tuple(int(v) for v in spec)
+            if spec[0] < 0 or spec[1] < 0 or spec[2] < 1 or spec[3] < 1:
+                raise ValueError("run_video_matte: the window roi = (y0, x0, h, w) needs y0, x0 >= 0 and h, w >= 1, got %r" % (spec,))
+        if isinstance(margin, bool) or not isinstance(margin, (int, np.integer)) or margin < 0:
+            raise ValueError("run_video_matte: roi_margin is a number of pixels >= 0 (an integer), got %r" % (margin,))
+        if alphas is not None:
+            raise ValueError("run_video_matte: roi belongs to the trimap flow; the alphas flow (VideoMatting108: trimaps from "
+                             "ground-truth alpha) has no region-of-interest route")
+        if backgrounds is not None:
+            raise ValueError("run_video_matte: roi takes no per-frame `backgrounds` (they belong to the alphas flow)")
+        if work_scale is not None:
+            raise ValueError("run_video_matte: roi and work_scale exclude each other (a window at the working resolution is out "
+                             "of scope); give one of them")
+        if len(frames) > 0 and (isinstance(frames, (list, tuple, np.ndarray)) or torch.is_tensor(frames)):
+            f0 = _as_tensor(frames[0])
+            if f0.dtype != torch.uint8:
+                raise ValueError("run_video_matte: roi takes uint8 [H,W,3] frames (float frames have no region-of-interest "
+                                 "route), got %s" % f0.dtype)
+            if not isinstance(spec, str):
+                _roi.check_window(spec, f0.shape[0], f0.shape[1], "run_video_matte: roi")
+        return spec, int(margin)
+
+    def place_tracking(self, unknown, H, W):
+        self.HW, self.tracking = (H, W), True
+        if self.spec == "auto":
+            h, w = _roi.window_size(unknown, H, W, self.margin)
+            self.windows, at = [], (0, 0)
+            for box in unknown:
+                at = _roi.window_origin(box, h, w, H, W, at)
+                self.windows.append(at + (h, w))
+            return
+        win = _roi.check_window(self.spec, H, W, "run_video_matte: roi")
+        for t, box in enumerate(unknown):
+            if not _roi.contains(win, box):
+                raise ValueError("run_video_matte: the window roi = %r does not hold the unknown band of frame %d's mask (rows "
+                                 "%d ... %d, columns %d ... %d)" % (win, t, box[0], box[2], box[1], box[3]))
+        self.windows = [win] * len(unknown)
+
+    def place_static(self, nonbg, H, W, T):
+        """nonbg: {frame: the non-background box of the source given for it}"""
+        self.HW = (H, W)
+        if self.spec == "auto":
+            box = _roi.union(nonbg.values()) or (H, W, -1, -1)
+            h, w = _roi.window_size([box], H, W, self.margin)
+            win = _roi.window_origin(box, h, w, H, W) + (h, w)
+        else:
+            win = _roi.check_window(self.spec, H, W, "run_video_matte: roi")
+            for t, box in sorted(nonbg.items()):
+                if not _roi.contains(win, box):
+                    raise ValueError("run_video_matte: the window roi = %r does not hold the trimap / label map of frame %d (its "
+                                     "classes other than background: rows %d ... %d, columns %d ... %d)"
+                                     % (win, t, box[0], box[2], box[1], box[3]))
+        self.windows = [win] * T
+
+    def window(self, i):
+        return self.windows[i]
+
+    @property
+    def size(self):
+        return None if not self.windows else tuple(self.windows[0][2:])
+
+    def stage(self, f, i, dev):
+        """_stage_frame's tuple for frame ``i``'s window.  The upload event is waited for HERE: the crop reads the upload on the
+        launch stream, so no event is left for the caller."""
+        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != 3:
+            raise ValueError("run_video_matte: roi takes uint8 [H,W,3] frames (float frames have no region-of-interest "
+                             "route), got %s %s" % (f.dtype, tuple(f.shape)))
+        if tuple(f.shape[:2]) != self.HW:
+            raise ValueError("run_video_matte: frame %d is %dx%d, the trimaps the window was placed in are %dx%d"
+                             % ((i,) + tuple(f.shape[:2]) + self.HW))
+        ready = getattr(f, "_otvm_ready", None)
+        self.full = f.to(dev, non_blocking=True).contiguous()
+        if ready is not None:
+            torch.cuda.current_stream(dev).wait_event(ready)
+        win = self.windows[i]
+        if self.tracking:
+            # this frame's own trimap, at H x W: what the paste shows outside the window; nothing of it outlives the step
+            self.outside = self.plan.sources[i].convert(self.plan.model, dev)
+            fg, self.tri, _ = _roi.crop(win, frame=self.full, trimap=self.outside)
+        else:
+            fg = _roi.crop(win, frame=self.full)[0]
+        return fg, fg, win[2], win[3], True, None, None
+
+    def take_trimap(self):
+        tri, self.tri = self.tri, None
+        return tri
+
+    def finish(self, i, out, engine, dev):
+        """(alpha, alpha_u8, trimap) at H x W; with ``foreground`` the pasted F is kept for foreground_bytes().  A static window
+        also files the box of the frame's output trimap, for roi_clipped."""
+        tri = out[1][0, 0].contiguous()
+        if not self.tracking:
+            if self.rows is None:
+                self.rows = torch.empty((len(self.windows), 8), dtype=torch.int32, device=dev)
+            _roi.trimap_bbox(tri, self.rows[i])
+            self.seen.append(i)
+        alpha, u8, trimap, self.fgr_full = _roi.paste(
+            self.windows[i], self.HW[0], self.HW[1], out[3][0, 0, 0], tri, engine.last_fgr if self.foreground else None, self.full,
+            self.rgb, self.outside, ("alpha", "alpha_u8", "trimap") + (("fgr",) if self.foreground else ()))
+        self.outside = None
+        return alpha, u8, trimap
+
+    def foreground_bytes(self, i, alpha, dev):
+        """(rgba, comp) at H x W of ``alpha`` and the pasted F over frame ``i``'s new background: otvm_fgr_outputs"""
+        nb = None if self.new_background is None else _background_at(self.new_background, i, dev, self.bg_cache)
+        if isinstance(nb, tuple):
+            background_colour(nb, "run_video_matte")
+        return guided.foreground_bytes(alpha, self.fgr_full, self.rgb, nb, "run_video_matte")
+
+    def result(self):
+        """roi, roi_size and roi_clipped (ONE read-back of the boxes, after the last frame)"""
+        clipped = []
+        if self.rows is not None:
+            H, W = self.HW
+            boxes = _roi.boxes_of(self.rows)[1]
+            for i in sorted(self.seen):
+                y0, x0 = self.windows[i][:2]
+                b = boxes[i]
+                if not _roi.is_empty(b) and _roi.touched_sides(self.windows[i], (b[0] + y0, b[1] + x0, b[2] + y0, b[3] + x0), H, W):
+                    clipped.append(i)
+        return dict(roi=list(self.windows or []), roi_size=self.size, roi_clipped=clipped)
+
+
 class _Stabilisation:
     """``stabilise``'s side of a frame step: the temporal filter of alpha (otvm_amd/temporal.py) behind the frame -- and behind
     _WorkingResolution.finish -- on the launch stream.  refuse() is the host-only part, before anything is uploaded."""
@@ -416,13 +620,15 @@ class _Collector:
         if self.comp is not None:
             self.comp[i] = self.keep(comp)
 
-    def result(self, metrics=None, schedule=None, work_size=None):
+    def result(self, metrics=None, schedule=None, work_size=None, roi=None):
         res = dict(alpha=torch.stack(self.alpha), alpha_u8=torch.stack(self.u8), trimap=torch.stack(self.trimap),
                    bank_frames=self.bank)
         if schedule is not None:
             res.update(anchor_frames=self.anchors, schedule=schedule)
         if work_size is not None:
             res["work_size"] = work_size
+        if roi is not None:
+            res.update(roi)
         if self.raw is not None:
             res["alpha_raw"] = torch.stack(self.raw)
         if self.rgba is not None:
@@ -438,7 +644,7 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                     frames_are_rgb=False, on_frame=None, device=None, keep_on_device=False, gt_alpha_u8=None,
                     gt_mask_u8=None, gt_mask=None, gt_image_metrics=False, gt_flow_metrics=False, foreground=False,
                     new_background=None, keyframes=None, work_scale=None, work_radius=2, work_eps=1e-4, on_foreground=None,
-                    mask=None, masks=None, stabilise=None):
+                    mask=None, masks=None, stabilise=None, roi=None, roi_margin=32):
     """Matte one sequence.
 
     model       : EvalModel (optionally wrapped in nn.DataParallel), on the GPU
@@ -500,6 +706,28 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                   property on synthetic clips, not by quality on real footage, and the default parameters are PLACEHOLDERS.
                   Refused for float frames, with ``backgrounds`` and for a keyframe schedule that is not in natural order (a
                   backward sweep); not available in run_video_matte_batch.
+    roi         : None (off: a frame issues exactly the launches it issues without the option), "auto" or a window (y0, x0, h, w):
+                  region-of-interest matting.  Every frame (uint8 [H,W,3] only) is cropped on the device to an h x w window, the
+                  network runs there -- the memory schedule, large-input rule included, is evaluated at h x w -- and alpha, the
+                  trimap (with ``foreground`` also F) are pasted back into H x W (otvm_amd/roi.py).  Checked BY DEFINITION ONLY:
+                  the result is, bit for bit, the matte of the cropped clip pasted back.  It is NOT the full-frame result -- the
+                  decoder's pyramid pooling sees the window, not the frame -- and with no trained checkpoint here nobody can say
+                  how the two compare on real footage.  "auto" with ``masks`` TRACKS: a pre-pass converts every mask and takes the
+                  box of its unknown band (one read-back), the largest box plus ``roi_margin`` on every side, rounded up to a
+                  multiple of 32, is the clip's one window size, and each frame's window is centred on its own box; outside the
+                  window alpha is 1 / 0 by the frame's own trimap, and the window holds the whole unknown band by construction.
+                  "auto" with ``trimap`` / ``mask`` / ``keyframes`` places ONE window for the clip round the classes other than
+                  background of all the sources (label maps count with their labels 1 and 2); everything outside it is
+                  background and is never looked at, so the subject must STAY inside: the result's roi_clipped lists the frames
+                  whose propagated trimap reaches a side of the window that is not a side of the frame.  A window given by the
+                  caller serves every frame of any route and is refused when a source does not fit in it (``masks``: the unknown
+                  band of any frame).  alpha, alpha_u8, trimap, fgr_u8, comp_u8, alpha_raw, on_frame's alpha / u8 and the metrics
+                  are at H x W (on_frame's ``out`` is the network's, at h x w); the foreground bytes are made at full resolution
+                  from the pasted planes, ``stabilise`` runs behind the paste.  The result gains roi=[(y0, x0, h, w) per frame],
+                  roi_size=(h, w) and roi_clipped.  Every window size is an engine plan of its own and NOTHING is evicted here: a
+                  process that mattes many clips drops them itself (EvalModel.drop_plans).  Refused for float frames, the
+                  ``alphas`` flow, ``backgrounds`` and together with ``work_scale``; not available in run_video_matte_batch.
+    roi_margin  : pixels kept round the box on every side by roi="auto" (default 32: a PLACEHOLDER nobody tuned on real footage)
     Returns dict(alpha=[T,H,W] float32, alpha_u8=[T,H,W] uint8 (truncated, eval.py:209), trimap=[T,3,H,W],
     bank_frames=[per frame: ids of the frames resident in the memory bank after that frame's update]) and, when ``keyframes``
     was given, anchor_frames=[per frame: those of them that are anchors], schedule=[the steps issued, keyframe_schedule's tuples].
@@ -508,7 +736,7 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
     T = len(frames)
     dev = device or next(model.parameters()).device
     plan = _ClipPlan(model, frames, trimap, alphas, keyframes, mask, masks, backgrounds, work_scale, work_radius, work_eps, skip,
-                     max_num)
+                     max_num, roi, roi_margin)
     stab = temporal.options_of(stabilise)
     if stab is not None:
         _Stabilisation.refuse(plan, frames, backgrounds)
@@ -517,6 +745,7 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
     foreground = bool(foreground) or new_background is not None
     work = (None if work_scale is None else
             _WorkingResolution(work_scale, work_radius, work_eps, foreground, frames_are_rgb, new_background))
+    region = plan.region = None if plan.roi is None else _RegionOfInterest(plan, foreground, frames_are_rgb, new_background)
     col = _Collector(T, keep_on_device, foreground, new_background is not None, on_foreground, raw=stab is not None)
     metrics = (ClipMetrics(dev, image_metrics=gt_image_metrics, flow_metrics=gt_flow_metrics) if gt_alpha_u8 is not None
                else None)
@@ -529,6 +758,7 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
             if stab is not None:
                 stab.check_frame(f)
             fg, bg, H, W, rgb_applies, ready, ready_b = (work.stage(f, dev) if work is not None else
+                                                         region.stage(f, i, dev) if region is not None else
                                                          _stage_frame(f, b, dev, frames_are_rgb))
             extra = {"_frames_rgb": bool(frames_are_rgb)} if rgb_applies else {}
             if ready_b is not None:
@@ -543,7 +773,7 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                     extra["_inputs_ready"] = ready
                 else:
                     torch.cuda.current_stream(dev).wait_event(ready)
-            plan.check_masks(i, (H, W) if work is None else work.full.shape[:2])
+            plan.check_masks(i, work.full.shape[:2] if work is not None else region.HW if region is not None else (H, W))
             a, tri_gt, more = plan.inputs(i, kind, first_frame, H, W, dev)
             if i == plan.k0 - 1:
                 core.drop_non_anchors()                           # the backward sweep starts from the keyframes alone
@@ -553,12 +783,17 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
             if foreground:
                 # (working resolution: the composite is made at full resolution by work.finish, not by the engine)
                 # (stabilise: made behind the temporal filter, from the stabilised alpha)
-                core.set_background(None if new_background is None or work is not None or stab is not None
+                # (roi: made behind the paste, at full resolution, by region.foreground_bytes)
+                core.set_background(None if new_background is None or work is not None or stab is not None or region is not None
                                     else _background_at(new_background, i, dev, bg_cache))
             out = model(a, fg, bg, tri=None, tri_gt=tri_gt, first_frame=first_frame, last_frame=last_frame,
                         memorize=memorize, max_memory_num=max_memory_num, large_input=large, _frame_id=i, **extra, **more)
-            alpha, u8, rgba, comp = out[3][0, 0, 0], core._engine.last_alpha_u8, None, None
-            if work is not None:
+            alpha, u8, rgba, comp, tri_out = out[3][0, 0, 0], core._engine.last_alpha_u8, None, None, out[1][0, 0]
+            if region is not None:
+                alpha, u8, tri_out = region.finish(i, out, core._engine, dev)
+                if foreground and stab is None:
+                    rgba, comp = region.foreground_bytes(i, alpha, dev)
+            elif work is not None:
                 alpha, u8, rgba, comp = work.finish(i, fg, alpha, core._engine, dev, make_bytes=stab is None)
             elif foreground:
                 rgba, comp = core._engine.last_rgba_u8, core._engine.last_comp_u8
@@ -567,8 +802,11 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                 # the frame as it was staged (its upload is behind the launch stream: the model waited for it), the alpha at
                 # H x W and the trimap the network put out, at the resolution it ran at
                 raw = alpha
-                alpha, u8 = stab.step(fg if work is None else work.full, alpha, out[1][0, 0], 1 if work is None else work_scale, dev)
-                if work is not None and foreground:
+                full = region.full if region is not None else fg if work is None else work.full
+                alpha, u8 = stab.step(full, alpha, tri_out, 1 if work is None else work_scale, dev)
+                if region is not None and foreground:
+                    rgba, comp = region.foreground_bytes(i, alpha, dev)
+                elif work is not None and foreground:
                     rgba, comp = work.foreground_bytes(i, alpha, dev)
                 elif foreground:
                     nb = None if new_background is None else _background_at(new_background, i, dev, bg_cache)
@@ -581,12 +819,13 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                 _metrics_add(metrics, u8, i, gt_alpha_u8, gt_mask_u8, gt_mask, dev)
             if on_frame is not None:
                 on_frame(i, alpha, u8, out)
-            col.put(i, alpha, u8, out[1][0, 0], rgba, comp, raw=raw)
+            col.put(i, alpha, u8, tri_out, rgba, comp, raw=raw)
     if metrics is not None and not plan.natural:
         # the pair terms (dtSSD, MESSDdt) depend on the order: fed in natural frame order from the kept 8-bit alphas
         for i in range(T):
             _metrics_add(metrics, col.u8[i].to(dev), i, gt_alpha_u8, gt_mask_u8, gt_mask, dev)
-    return col.result(metrics, list(plan.steps) if plan.keyed else None, None if work is None else work.size)
+    return col.result(metrics, list(plan.steps) if plan.keyed else None, None if work is None else work.size,
+                      None if region is None else region.result())
 
 
 def _metrics_add(metrics, u8, i, gt_alpha_u8, gt_mask_u8, gt_mask, dev):
@@ -600,7 +839,7 @@ def _metrics_add(metrics, u8, i, gt_alpha_u8, gt_mask_u8, gt_mask, dev):
 def run_video_matte_batch(model, clips, trimaps=None, alphas=None, backgrounds=None, skip=10, max_num=5, frames_are_rgb=False,
                           device=None, keep_on_device=False, on_frame=None, gt_alpha_u8=None, gt_mask=None,
                           gt_image_metrics=False, gt_flow_metrics=False, foreground=False, new_background=None, keyframes=None,
-                          work_scale=None, mask=None, masks=None):
+                          work_scale=None, mask=None, masks=None, roi=None):
     """Matte B sequences of one resolution in LOCK-STEP (round 3): frame i of every clip goes through the network in one
     batched step (EvalModel.forward_batch: one launch per layer over the B images, per-sequence memory banks).
     clips: list of B frame arrays ([T_b,H,W,3] uint8 / float, BGR unless frames_are_rgb); trimaps: list of B first-frame
@@ -626,6 +865,9 @@ def run_video_matte_batch(model, clips, trimaps=None, alphas=None, backgrounds=N
     if mask is not None or masks is not None or (trimaps is not None and any(isinstance(t, Mask) for t in trimaps)):
         raise ValueError("run_video_matte_batch: trimaps from masks (mask / masks / a Mask) are a single-clip feature "
                          "(run_video_matte); lock-step batches take trimaps")
+    if roi is not None:
+        raise ValueError("run_video_matte_batch: roi (region-of-interest matting) is a single-clip feature (run_video_matte); the "
+                         "clips of a lock-step batch share one resolution, a window per clip would not")
     B = len(clips)
     lens = [len(c) for c in clips]
     T = max(lens)
