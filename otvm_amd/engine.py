@@ -125,7 +125,7 @@ PPM_ALGEBRA = os.environ.get("OTVM_PPM_ALGEBRA", "1") != "0"       # the four PP
 # OTVM_AUTOTUNE=0 keeps the built-in heuristic (thresholds tuned by hand on the 1080p frame).
 AUTOTUNE = os.environ.get("OTVM_AUTOTUNE", "1") != "0"
 _TUNE_CACHE = {}
-TUNE_LOG = []           # (signature, chosen code, {code: ms}) of every shape timed in this process (tools / DESIGN numbers)
+TUNE_LOG = []           # (name, signature, chosen code, {code: ms}) of every choice timed in this process (tools / DESIGN numbers)
 # OTVM_TUNE_FILE=path: choices are loaded from / saved to a JSON file, so a later process (a profiler run, a service
 # restart) launches the tuned configurations without timing anything.
 TUNE_FILE = os.environ.get("OTVM_TUNE_FILE")
@@ -214,6 +214,70 @@ def share_tune_cache(src=0):
     dist.broadcast_object_list(obj, src=src)
     if dist.get_rank() != src:
         _TUNE_CACHE.update(obj[0])
+
+
+class _EventClock:
+    """Device time for _time_candidates: the handle of the current stream, mark() = an event recorded on it, ms(pairs) = one wait
+    for the device, then the milliseconds between the marks of every pair.  (The tuner's CPU tests pass a fake in its place.)"""
+
+    def __init__(self, dev):
+        self.dev, self.stream = dev, torch.cuda.current_stream(dev).cuda_stream
+
+    def mark(self):
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        return e
+
+    def ms(self, pairs):
+        torch.cuda.synchronize(self.dev)
+        return [a.elapsed_time(b) for a, b in pairs]
+
+
+def _time_candidates(eng, clock, steps_of, order, reps, warm=(), lead=0):
+    """THE plan-time timing protocol.  ``steps_of(c)`` returns the launch steps ``(fn, args, label, ...)`` of ONE repetition of
+    candidate ``c`` (and may set a parameter block to ``c`` first).  One repetition of every candidate in ``warm`` is thrown away;
+    then every entry of ``order`` (candidates may repeat) is one measurement: ``lead`` untimed repetitions, ``reps`` timed ones
+    between two marks of ``clock``.  Returns {candidate: ms per repetition, the minimum over its measurements}.  Every return code
+    is checked; the launches labelled "conv " are counted into ``eng.conv_calls`` (as FramePlan.run counts them)."""
+    def issue(c, n):
+        for _ in range(n):
+            for st in steps_of(c):
+                L.check(st[0](*st[1], clock.stream), st[2])
+                eng.conv_calls += int(st[2].startswith("conv "))
+    for c in warm:
+        issue(c, 1)
+    marks = []
+    for c in order:
+        issue(c, lead)
+        m0 = clock.mark()
+        issue(c, reps)
+        marks.append((m0, clock.mark()))
+    ms = {}
+    for c, t in zip(order, clock.ms(marks)):
+        ms[c] = min(ms.get(c, t / reps), t / reps)
+    return ms
+
+
+def _choose(key, label, sig, measure, forced=None, default=None, settle=None):
+    """THE ladder of every plan-time choice: ``forced`` if the route's switch forces a value, else the cached choice of ``key``,
+    else ``default`` if timing is off (returned, not stored) -- None = does not apply -- else the fastest of ``measure()`` =
+    {candidate: ms}, or what ``settle(ms, fastest)`` makes of it: stored under ``key``, logged with the report signature ``sig``."""
+    for choice in (forced, _TUNE_CACHE.get(key), default):
+        if choice is not None:
+            return choice
+    ms = measure()
+    choice = min(ms, key=ms.get)
+    if settle is not None:
+        choice = settle(ms, choice)
+    _TUNE_CACHE[key] = choice
+    TUNE_LOG.append((label, sig, choice, ms))
+    return choice
+
+
+def _save_choices_timed_since(n_logged):
+    """End of a tuning phase that began with ``n_logged`` entries in TUNE_LOG: one write of the tune file if it timed anything."""
+    if len(TUNE_LOG) > n_logged:
+        _save_tune_file()
 
 
 def _rup(x, m):
@@ -1232,57 +1296,37 @@ class FramePlan:
                 int(bool(p.residual)), p.res_ld, int(bool(p.gn_stats)), int(bool(p.in_scale)), int(bool(p.splitk_ws)), p.precision,
                 max(1, p.batch), int(bool(p.res_scale)), int(bool(p.in_res)))
 
-    def _time_conv(self, p, code, stream, reps=3):
-        p.tune = code
-        fn = self.lib.otvm_conv2d
-        self.e.conv_calls += 1 + reps
-        L.check(fn(C.byref(p), stream), "autotune warm-up")
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn(C.byref(p), stream)
-        e1.record()
-        return e0, e1, reps
+    def _time_conv_codes(self, p, name):
+        codes = (C.c_int * 128)()
+        n = int(self.lib.otvm_conv2d_candidates(C.byref(p), codes, 128))
+        cands = [0] + [int(codes[i]) for i in range(n)]           # 0 = the built-in heuristic, the incumbent
+        if not WAVE_TILE:                                         # (the fragment-major weights alone do not switch the one-wave tile on)
+            cands = [c for c in cands if c // 16 - 1 != 9]
+        step = (self.lib.otvm_conv2d, (C.byref(p),), "conv " + name)
+
+        def steps_of(c):
+            p.tune = c
+            return (step,)
+        # the first timing of a layer runs on cold caches and ramping clocks (measured: the same kernel 14 % slower
+        # as first candidate than as second): a throw-away pass first, the incumbent timed again at the end
+        return _time_candidates(self.e, _EventClock(self.dev), steps_of, cands + [0], 3, warm=(0, 0, 0), lead=1)
 
     def tune_convs(self, convs):
         """Pick otvm_conv_params.tune for every (params, name) in ``convs`` (cached per layer signature)."""
         if not (AUTOTUNE and self.e.precision == L.PREC_F16X3):
             return
-        stream = torch.cuda.current_stream(self.dev).cuda_stream
-        codes = (C.c_int * 128)()
-        timed_any = False
+        n_logged = len(TUNE_LOG)
         for p, name in convs:
             sig = self._signature(p)
-            if sig not in _TUNE_CACHE:
-                n = int(self.lib.otvm_conv2d_candidates(C.byref(p), codes, 128))
-                cands = [0] + [int(codes[i]) for i in range(n)]           # 0 = the built-in heuristic, the incumbent
-                if not WAVE_TILE:                                         # (the fragment-major weights alone do not switch the one-wave tile on)
-                    cands = [c for c in cands if c // 16 - 1 != 9]
-                # the first timing of a layer runs on cold caches and ramping clocks (measured: the same kernel 14 % slower
-                # as first candidate than as second): a throw-away pass first, the incumbent timed again at the end
-                self._time_conv(p, 0, stream, reps=2)
-                timed = [(c,) + self._time_conv(p, c, stream) for c in cands + [0]]
-                torch.cuda.synchronize(self.dev)
-                ms = {}
-                for c, e0, e1, r in timed:
-                    t = e0.elapsed_time(e1) / r
-                    ms[c] = min(ms.get(c, t), t)
-                best = min(ms, key=ms.get)
-                if ms[best] > 0.97 * ms[0]:                                # keep the incumbent unless clearly beaten
-                    best = 0
-                _TUNE_CACHE[sig] = best
-                TUNE_LOG.append((name, sig, best, ms))
-                timed_any = True
-            p.tune = _TUNE_CACHE[sig]
-        if timed_any:
-            _save_tune_file()
+            p.tune = _choose(sig, name, sig, lambda: self._time_conv_codes(p, name),
+                             settle=lambda ms, fastest: fastest if ms[fastest] <= 0.97 * ms[0] else 0)   # keep the incumbent unless clearly beaten
+        _save_choices_timed_since(n_logged)
 
     def _resolve_stm128(self, timed):
         """Every planes-128 STM identity block of the plan: fused (one launch, pixel tile 1 = 8x16 / 2 = 8x8 / 3 = 4x8) or its three
         convolution launches (0), whichever is faster on this map -- timed once per (map, batch) with the buffers holding random
         values (autotune), cached beside the conv tuner's choices; FUSE_STM_BLOCK128 = 2 or no tuner: fused, tile from the map."""
-        stream = torch.cuda.current_stream(self.dev).cuda_stream
-        timed_any = False
+        n_logged = len(TUNE_LOG)
         for S in self._stm128:
             i = 0
             while i < len(S):
@@ -1291,37 +1335,15 @@ class FramePlan:
                     i += 1
                     continue
                 _, fused, U, q, name = st
-                key = (-128, q.H, q.W, max(1, q.batch), q.x_ld, q.y_ld)
-                if FUSE_STM_BLOCK128 >= 2 or not timed:
-                    choice = _TUNE_CACHE.get(key, -1) if FUSE_STM_BLOCK128 < 2 else (STM128_TILE or -1)
-                elif key in _TUNE_CACHE:
-                    choice = _TUNE_CACHE[key]
-                else:
-                    def run(c, reps):
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record()
-                        for _ in range(reps):
-                            if c == 0:
-                                for u in U:
-                                    u[0](*u[1], stream)
-                            else:
-                                q.tile = c
-                                L.check(fused[0](*fused[1], stream), name)
-                        e1.record()
-                        return e0, e1, reps
-                    self.e.conv_calls += 3 * 7 + 3 * 7                  # (counted like the conv tuner's launches)
-                    run(0, 2)
-                    timed_ = [(c,) + run(c, 3) for c in (0, 1, 2, 3, 0, 1, 2, 3)]
-                    torch.cuda.synchronize(self.dev)
-                    ms = {}
-                    for c, e0, e1, r in timed_:
-                        t = e0.elapsed_time(e1) / r
-                        ms[c] = min(ms.get(c, t), t)
-                    choice = min(ms, key=ms.get)
-                    _TUNE_CACHE[key] = choice
-                    TUNE_LOG.append((name + " (fused bottleneck: 0 = three launches, 1 / 2 / 3 = fused on 8x16 / 8x8 / 4x8 pixels)",
-                                     (q.H, q.W, 512, q.x_ld, 512, q.y_ld, 3, 3, 1, 1, 1), choice, ms))
-                    timed_any = True
+
+                def steps_of(c):
+                    q.tile = c                                           # (the three launches of route 0 do not read it)
+                    return (fused,) if c else U
+                choice = _choose((-128, q.H, q.W, max(1, q.batch), q.x_ld, q.y_ld),
+                                 name + " (fused bottleneck: 0 = three launches, 1 / 2 / 3 = fused on 8x16 / 8x8 / 4x8 pixels)",
+                                 (q.H, q.W, 512, q.x_ld, 512, q.y_ld, 3, 3, 1, 1, 1),
+                                 lambda: _time_candidates(self.e, _EventClock(self.dev), steps_of, (0, 1, 2, 3) * 2, 3, warm=(0, 0)),
+                                 forced=(STM128_TILE or -1) if FUSE_STM_BLOCK128 >= 2 else None, default=None if timed else -1)
                 if choice == 0:
                     S[i:i + 1] = U
                     i += len(U)
@@ -1330,8 +1352,7 @@ class FramePlan:
                     S[i] = fused
                     i += 1
         self._stm128 = []
-        if timed_any:
-            _save_tune_file()
+        _save_choices_timed_since(n_logged)
 
     def autotune(self):
         if not (AUTOTUNE and self.e.precision == L.PREC_F16X3):
@@ -1573,8 +1594,7 @@ class FramePlan:
         map, timed once per (map, batch) with both routes warm, the minimum of several alternating repetitions (the buffers hold
         random values: autotune), cached beside the conv tuner's choices; 2: folded wherever the library takes every reader; 0, or
         the training forward (its decoder tensors are read back: keep_hid_d): the pass."""
-        stream = torch.cuda.current_stream(self.dev).cuda_stream
-        timed_any = False
+        n_logged = len(TUNE_LOG)
         for m in self._upfold:
             self.upfold_routes[m["name"]] = 0
             if FOLD_UPSAMPLE <= 0 or self.e.keep_hid_d or not m["readers"]:
@@ -1597,37 +1617,11 @@ class FramePlan:
             if folded is None:
                 continue
             key = (-2, src.H, src.W, max(1, src.B), src.C, src.ld) + tuple(v for r in m["readers"] for v in (r[2].Cin, r[2].Cout, r[2].act))
-            if FOLD_UPSAMPLE >= 2:
-                choice = 1
-            elif key in _TUNE_CACHE:
-                choice = _TUNE_CACHE[key]
-            elif not timed:
-                choice = 0
-            else:
-                routes = {0: [m["step"]] + [r[1] for r in m["readers"]], 1: folded}
-
-                def run(c, reps):
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(reps):
-                        for st in routes[c]:
-                            L.check(st[0](*st[1], stream), st[2])
-                    e1.record()
-                    return e0, e1, reps
-                self.e.conv_calls += 2 * (2 + 4 * 3) * len(folded)              # (counted like the conv tuner's launches)
-                run(0, 2)
-                run(1, 2)
-                timed_ = [(c,) + run(c, 3) for c in (0, 1, 0, 1, 0, 1, 0, 1)]
-                torch.cuda.synchronize(self.dev)
-                ms = {}
-                for c, e0, e1, r in timed_:
-                    t = e0.elapsed_time(e1) / r
-                    ms[c] = min(ms.get(c, t), t)
-                choice = min(ms, key=ms.get)
-                _TUNE_CACHE[key] = choice
-                TUNE_LOG.append((m["name"] + " (2x upsampling: 0 = pass + reader convs, 1 = read at source resolution by the convs)",
-                                 (2 * src.H, 2 * src.W, src.C, src.ld, src.C, m["out"].ld, 1, 1, 1, 0, 1), choice, ms))   # (a layer-like signature: reports)
-                timed_any = True
+            routes = {0: [m["step"]] + [r[1] for r in m["readers"]], 1: folded}
+            choice = _choose(key, m["name"] + " (2x upsampling: 0 = pass + reader convs, 1 = read at source resolution by the convs)",
+                             (2 * src.H, 2 * src.W, src.C, src.ld, src.C, m["out"].ld, 1, 1, 1, 0, 1),
+                             lambda: _time_candidates(self.e, _EventClock(self.dev), routes.get, (0, 1) * 4, 3, warm=(0, 0, 1, 1)),
+                             forced=1 if FOLD_UPSAMPLE >= 2 else None, default=None if timed else 0)
             if choice:
                 at = lambda S, st: next(i for i, q in enumerate(S) if q is st)   # noqa: E731 -- (by identity: tuples of ctypes objects)
                 del m["S"][at(m["S"], m["step"])]
@@ -1637,8 +1631,7 @@ class FramePlan:
                 for b in range(max(1, m["out"].B)):                             # nobody writes these channels any more: zeros, not
                     m["out"].torch(b).zero_()                                   # the timing's leftovers, for the stage diagnostics
         self._upfold = []
-        if timed_any:
-            _save_tune_file()
+        _save_choices_timed_since(n_logged)
 
     def maxpool(self, S, x, out):
         S.append((self.lib.otvm_maxpool3x3s2_b, (x.ptr, x.H, x.W, x.C, x.ld, out.ptr, out.ld, x.B, x.bs, out.bs), "maxpool"))

@@ -554,7 +554,7 @@ def test_graph_replay_equals_direct_launches(synth_sd):
     assert torch.equal(outs[0]["alpha"], outs[1]["alpha"]) and torch.equal(outs[0]["trimap"], outs[1]["trimap"])
 
 
-def test_autotuned_plan_matches_heuristic_plan(synth_sd):
+def test_autotuned_plan_matches_heuristic_plan(synth_sd, monkeypatch):
     """The plan-time autotuner (engine.AUTOTUNE) only re-orders fp32 sums: a clip matted with tuned configurations stays
     within the parity bound of the same clip matted with the built-in heuristic, two engines of one process share the
     cached choices (bit-identical results), and the tuner really timed alternatives."""
@@ -575,9 +575,10 @@ def test_autotuned_plan_matches_heuristic_plan(synth_sd):
             return run_video_matte(m.cuda().eval(), frames, trimap=tri, skip=3, max_num=3)
         finally:
             engine.AUTOTUNE = old
+    monkeypatch.setattr(engine, "_TUNE_CACHE", {})               # no signature cached by an earlier test: the first run times
     n0 = len(engine.TUNE_LOG)
     a = matte(True)
-    assert len(engine.TUNE_LOG) > n0 or any(sig[0] == 160 // 1 or True for _, sig, _, _ in engine.TUNE_LOG)
+    assert len(engine.TUNE_LOG) > n0
     assert all(len(ms) >= 2 for _, _, _, ms in engine.TUNE_LOG)
     b = matte(True)
     c = matte(False)
