@@ -74,7 +74,10 @@ const char* otvm_last_error(void);
                                   likewise the patch conv with an upsampled source: otvm_conv2d_up and
                                   otvm_conv2d_accepts_upsampled_input with otvm_conv_up_params;
                                   likewise region-of-interest matting: otvm_trimap_bbox, otvm_roi_crop and otvm_roi_paste with
-                                  otvm_roi_bbox_params, otvm_roi_crop_params and otvm_roi_paste_params) */
+                                  otvm_roi_bbox_params, otvm_roi_crop_params and otvm_roi_paste_params;
+                                  likewise the tracking window of region-of-interest matting: otvm_roi_track with
+                                  otvm_roi_track_params, and otvm_roi_crop_at / otvm_roi_paste_at, which take the two structs above
+                                  as they are plus a device pointer) */
 int otvm_abi_version(void);
 
 /* ---------------------------------------------------------------- weights (load time) ----------
@@ -739,6 +742,33 @@ typedef struct otvm_roi_paste_params {
     float* fgr;                     /* [3,H,W] R, G, B */
 } otvm_roi_paste_params;
 int otvm_roi_paste(const otvm_roi_paste_params* p, void* stream);
+
+/* The tracking window (run_video_matte(roi="track")): the window's SIZE is fixed for a clip, its ORIGIN lives on the device, one
+ * (y0, x0) row per frame of an int32 [T,2] log, so that no frame waits for a read-back.  New symbols only; the structs above are
+ * taken as they are.
+ *
+ * otvm_roi_track: one small launch, integer arithmetic, no atomics, ordinary stores (two calls give equal bits); writes out[0..1].
+ *   box  : the eight words otvm_trimap_bbox wrote for the NEIGHBOURING frame; words 4 .. 7 (non-background) decide.
+ *   prev : the neighbour's origin (two words, clamped into the frame as read), the box then being in the neighbour's WINDOW; or
+ *          NULL: the box is in FRAME coordinates and the window is centred on it, (y0 + y1 + 1) / 2 - h / 2 clamped to the frame
+ *          (an empty box: (0, 0)).
+ *   With prev, each axis on its own: it HOLDS prev while the box keeps at least `hold` pixels from both window sides on that axis
+ *   (a window side that is the frame's side always counts as held) and recentres on the box, clamped, otherwise; an empty box
+ *   holds both.  hold >= 1.  otvm_amd/roi.py track_origin is the same policy on the host; the two are equal by test.           */
+typedef struct otvm_roi_track_params {
+    const int32_t* box;             /* 8 words */
+    const int32_t* prev;            /* 2 words or NULL */
+    int32_t* out;                   /* 2 words: row t of the log */
+    int H, W, h, w, hold;
+} otvm_roi_track_params;
+int otvm_roi_track(const otvm_roi_track_params* p, void* stream);
+
+/* otvm_roi_crop_at / otvm_roi_paste_at: otvm_roi_crop / otvm_roi_paste with the window's origin read by the kernel from `origin`,
+ * two int32 words on the device (a row of the log); p->y0 and p->x0 are not looked at.  What the kernel reads is CLAMPED to
+ * [0, H - h] x [0, W - w] before any address is formed from it: a stale or unwritten row cannot address outside the frame.
+ * 1 <= h <= H and 1 <= w <= W; every other refusal as in the forms above.  The kernel bodies are those of the forms above.   */
+int otvm_roi_crop_at(const otvm_roi_crop_params* p, const int32_t* origin, void* stream);
+int otvm_roi_paste_at(const otvm_roi_paste_params* p, const int32_t* origin, void* stream);
 
 /* ---------------------------------------------------------------- range guard / clear -----------
  * f16x3 splits fp32 operands into fp16 halves: |x| >= 65504 loses accuracy, >= 131008 becomes inf.

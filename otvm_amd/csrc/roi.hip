@@ -11,6 +11,13 @@
 // The box is a reduction: per thread in registers, per wave through shuffles, per workgroup through LDS, then one integer
 // min / max atomic per word and workgroup (at most 2048 workgroups, 8 words) onto words a one-wave kernel set to the empty boxes
 // just before on the same stream.  Integer min / max do not depend on the order of arrival.
+//
+// The tracking window (otvm_roi_track, otvm_roi_crop_at, otvm_roi_paste_at): the window's origin lives on the device, a row of an
+// int32 [T,2] log.  otvm_roi_track derives row t from the box row otvm_trimap_bbox wrote for the neighbouring frame and that
+// frame's origin -- two threads, one per axis, integer arithmetic, ordinary stores; otvm_amd/roi.py track_origin is the same policy
+// on the host.  The _at forms are the crop and the paste above with (y0, x0) read from such a row: the kernel bodies are shared
+// (the window side is never widened, so nothing about alignment depends on the origin), and whatever the row holds is clamped to
+// [0, H - h] x [0, W - w] before any address is formed from it.
 #include "common.h"
 
 namespace {
@@ -115,15 +122,22 @@ __global__ __launch_bounds__(256) void roi_bbox_kernel(const float* __restrict__
     }
 }
 
-// a thread takes four consecutive pixels of one WINDOW row
-template <bool VEC>
-__global__ __launch_bounds__(256) void roi_crop_kernel(const otvm_roi_crop_params p) {
+// the origin of a window whose origin lives on the device, clamped into the frame whatever the memory holds
+__device__ __forceinline__ int roi_origin_at(const int* __restrict__ origin, int axis, int full, int side) {
+    const int v = origin[axis], hi = full - side;
+    return v < 0 ? 0 : (v > hi ? hi : v);
+}
+
+// a thread takes four consecutive pixels of one WINDOW row; AT: the origin is read from `origin` (a row of the device log)
+template <bool VEC, bool AT>
+__global__ __launch_bounds__(256) void roi_crop_kernel(const otvm_roi_crop_params p, const int* __restrict__ origin) {
+    const int wy0 = AT ? roi_origin_at(origin, 0, p.H, p.h) : p.y0, wx0 = AT ? roi_origin_at(origin, 1, p.W, p.w) : p.x0;
     const int n4 = (p.w + 3) >> 2;
     const int64_t total = (int64_t)p.h * n4, P = (int64_t)p.H * p.W, M = (int64_t)p.h * p.w;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
         const int y = (int)(t / n4), x0 = (int)(t - (int64_t)y * n4) * 4;
         const int n = p.w - x0 < 4 ? p.w - x0 : 4;
-        const int64_t src = (int64_t)(y + p.y0) * p.W + (x0 + p.x0), dst = (int64_t)y * p.w + x0;
+        const int64_t src = (int64_t)(y + wy0) * p.W + (x0 + wx0), dst = (int64_t)y * p.w + x0;
         if (p.frame_out) {
             unsigned by[12];
 #pragma unroll
@@ -168,9 +182,10 @@ __global__ __launch_bounds__(256) void roi_crop_kernel(const otvm_roi_crop_param
     }
 }
 
-// a thread takes four consecutive pixels of one FRAME row
-template <bool VEC>
-__global__ __launch_bounds__(256) void roi_paste_kernel(const otvm_roi_paste_params p) {
+// a thread takes four consecutive pixels of one FRAME row; AT: as in the crop
+template <bool VEC, bool AT>
+__global__ __launch_bounds__(256) void roi_paste_kernel(const otvm_roi_paste_params p, const int* __restrict__ origin) {
+    const int wy0 = AT ? roi_origin_at(origin, 0, p.H, p.h) : p.y0, wx0 = AT ? roi_origin_at(origin, 1, p.W, p.w) : p.x0;
     const int n4 = (p.W + 3) >> 2;
     const int64_t total = (int64_t)p.H * n4, N = (int64_t)p.H * p.W, M = (int64_t)p.h * p.w;
     const float s = 1.f / 255.f;
@@ -178,9 +193,9 @@ __global__ __launch_bounds__(256) void roi_paste_kernel(const otvm_roi_paste_par
         const int y = (int)(t / n4), x0 = (int)(t - (int64_t)y * n4) * 4;
         const int n = p.W - x0 < 4 ? p.W - x0 : 4;
         const int64_t o = (int64_t)y * p.W + x0;
-        const bool row_in = y >= p.y0 && y < p.y0 + p.h;
+        const bool row_in = y >= wy0 && y < wy0 + p.h;
         // a group that lies inside the window altogether reads nothing of the frame's side
-        const bool all_in = row_in && x0 >= p.x0 && x0 + n <= p.x0 + p.w;
+        const bool all_in = row_in && x0 >= wx0 && x0 + n <= wx0 + p.w;
         float a[4], T[3][4], F[3][4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -227,8 +242,8 @@ __global__ __launch_bounds__(256) void roi_paste_kernel(const otvm_roi_paste_par
         for (int j = 0; j < 4; ++j) {
             const int x = x0 + j;
             a[j] = T[2][j] == 1.f ? 1.f : 0.f;
-            if (j < n && row_in && x >= p.x0 && x < p.x0 + p.w) {
-                const int64_t wi = (int64_t)(y - p.y0) * p.w + (x - p.x0);
+            if (j < n && row_in && x >= wx0 && x < wx0 + p.w) {
+                const int64_t wi = (int64_t)(y - wy0) * p.w + (x - wx0);
                 a[j] = p.win_alpha[wi];
 #pragma unroll
                 for (int k = 0; k < 3; ++k) T[k][j] = p.win_trimap[k * M + wi];
@@ -294,39 +309,119 @@ extern "C" int otvm_trimap_bbox(const otvm_roi_bbox_params* p, void* stream) {
     return 0;
 }
 
-#define ROI_REQUIRE_WINDOW(name, p)                                                                                                  \
-    OTVM_REQUIRE(roi_side_ok((p)->H) && roi_side_ok((p)->W), name ": the frame is 1 .. 16383 pixels a side, got %dx%d", (p)->H, (p)->W); \
-    OTVM_REQUIRE((p)->h >= 1 && (p)->w >= 1 && (p)->y0 >= 0 && (p)->x0 >= 0 && (p)->h <= (p)->H - (p)->y0 && (p)->w <= (p)->W - (p)->x0, \
-                 name ": a %dx%d window at (%d, %d) does not lie inside the %dx%d frame", (p)->h, (p)->w, (p)->y0, (p)->x0, (p)->H, (p)->W)
+namespace {
 
-extern "C" int otvm_roi_crop(const otvm_roi_crop_params* p, void* stream) {
-    OTVM_REQUIRE(p, "otvm_roi_crop: null parameters");
-    ROI_REQUIRE_WINDOW("otvm_roi_crop", p);
-    OTVM_REQUIRE(p->frame_out || p->trimap_out || p->labels_out, "otvm_roi_crop: no destination");
-    OTVM_REQUIRE((p->frame || !p->frame_out) && (p->trimap || !p->trimap_out) && (p->labels || !p->labels_out),
-                 "otvm_roi_crop: a destination without its source");
-    OTVM_REQUIRE((((uintptr_t)p->trimap | (uintptr_t)p->trimap_out) & 3) == 0, "otvm_roi_crop: misaligned trimap");
-    const bool vec = p->w % 4 == 0 && ((uintptr_t)p->trimap_out & 15) == 0 && (((uintptr_t)p->frame_out | (uintptr_t)p->labels_out) & 3) == 0;
-    const dim3 grid(roi_blocks(p->h, p->w));
-    if (vec) hipLaunchKernelGGL(roi_crop_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, *p);
-    else hipLaunchKernelGGL(roi_crop_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, *p);
-    OTVM_CHECK_LAUNCH("otvm_roi_crop");
+// thread 0 decides y, thread 1 decides x (otvm_amd/roi.py track_origin, axis by axis).  box: the neighbour's row, its non-background
+// box in words 4 .. 7 -- in the neighbour's window when `prev` is given, in the frame otherwise.
+__global__ __launch_bounds__(64) void roi_track_kernel(const int* __restrict__ box, const int* __restrict__ prev, int* __restrict__ out,
+                                                       int H, int W, int h, int w, int hold) {
+    const int a = threadIdx.x;
+    if (a >= 2) return;
+    const int full = a ? W : H, side = a ? w : h, top = full - side;
+    const bool empty = box[6] < box[4] || box[7] < box[5];
+    const int64_t lo = box[4 + a], hi = box[6 + a];
+    int o = 0;
+    bool held = empty;                                     // an empty box keeps the neighbour's origin ((0, 0) without one)
+    if (prev) {
+        o = roi_origin_at(prev, a, full, side);
+        held = held || ((lo >= hold || o == 0) && (side - 1 - hi >= hold || o == top));
+    }
+    if (!held) {
+        // (y0 + y1 + 1) // 2 - h // 2 of the box in frame coordinates; o is an integer, so it leaves the floor as it is
+        const int64_t c = o + ((lo + hi + 1) >> 1) - (side >> 1);
+        o = (int)(c < 0 ? 0 : (c > top ? top : c));
+    }
+    out[a] = o;
+}
+
+int roi_window_ok(const char* name, int H, int W, int h, int w) {
+    OTVM_REQUIRE(roi_side_ok(H) && roi_side_ok(W), "%s: the frame is 1 .. 16383 pixels a side, got %dx%d", name, H, W);
+    OTVM_REQUIRE(h >= 1 && w >= 1 && h <= H && w <= W, "%s: a %dx%d window does not fit the %dx%d frame", name, h, w, H, W);
     return 0;
 }
 
-extern "C" int otvm_roi_paste(const otvm_roi_paste_params* p, void* stream) {
-    OTVM_REQUIRE(p, "otvm_roi_paste: null parameters");
-    ROI_REQUIRE_WINDOW("otvm_roi_paste", p);
-    OTVM_REQUIRE(p->win_alpha && p->win_trimap, "otvm_roi_paste: null window alpha or window trimap");
-    OTVM_REQUIRE(p->alpha || p->alpha_u8 || p->trimap || p->fgr, "otvm_roi_paste: no output requested");
-    OTVM_REQUIRE(!p->fgr || (p->win_fgr && p->frame), "otvm_roi_paste: fgr needs the window's F planes and the frame");
+int roi_window_at_ok(const char* name, int H, int W, int y0, int x0, int h, int w) {
+    OTVM_REQUIRE(roi_side_ok(H) && roi_side_ok(W), "%s: the frame is 1 .. 16383 pixels a side, got %dx%d", name, H, W);
+    OTVM_REQUIRE(h >= 1 && w >= 1 && y0 >= 0 && x0 >= 0 && h <= H - y0 && w <= W - x0,
+                 "%s: a %dx%d window at (%d, %d) does not lie inside the %dx%d frame", name, h, w, y0, x0, H, W);
+    return 0;
+}
+
+// origin: NULL = the window is at (p->y0, p->x0); otherwise two device words, and p->y0 / p->x0 are not looked at
+int roi_crop_checked(const char* name, const otvm_roi_crop_params* p, const int32_t* origin, bool at, void* stream) {
+    OTVM_REQUIRE(p, "%s: null parameters", name);
+    if (at) {
+        OTVM_REQUIRE(origin && ((uintptr_t)origin & 3) == 0, "%s: the origin is two aligned int32 words on the device (y0, x0)", name);
+        if (int rc = roi_window_ok(name, p->H, p->W, p->h, p->w)) return rc;
+    } else if (int rc = roi_window_at_ok(name, p->H, p->W, p->y0, p->x0, p->h, p->w)) {
+        return rc;
+    }
+    OTVM_REQUIRE(p->frame_out || p->trimap_out || p->labels_out, "%s: no destination", name);
+    OTVM_REQUIRE((p->frame || !p->frame_out) && (p->trimap || !p->trimap_out) && (p->labels || !p->labels_out),
+                 "%s: a destination without its source", name);
+    OTVM_REQUIRE((((uintptr_t)p->trimap | (uintptr_t)p->trimap_out) & 3) == 0, "%s: misaligned trimap", name);
+    const bool vec = p->w % 4 == 0 && ((uintptr_t)p->trimap_out & 15) == 0 && (((uintptr_t)p->frame_out | (uintptr_t)p->labels_out) & 3) == 0;
+    const dim3 grid(roi_blocks(p->h, p->w));
+    hipStream_t s = (hipStream_t)stream;
+    if (at) {
+        if (vec) hipLaunchKernelGGL((roi_crop_kernel<true, true>), grid, dim3(256), 0, s, *p, origin);
+        else hipLaunchKernelGGL((roi_crop_kernel<false, true>), grid, dim3(256), 0, s, *p, origin);
+    } else {
+        if (vec) hipLaunchKernelGGL((roi_crop_kernel<true, false>), grid, dim3(256), 0, s, *p, nullptr);
+        else hipLaunchKernelGGL((roi_crop_kernel<false, false>), grid, dim3(256), 0, s, *p, nullptr);
+    }
+    OTVM_CHECK_LAUNCH(name);
+    return 0;
+}
+
+int roi_paste_checked(const char* name, const otvm_roi_paste_params* p, const int32_t* origin, bool at, void* stream) {
+    OTVM_REQUIRE(p, "%s: null parameters", name);
+    if (at) {
+        OTVM_REQUIRE(origin && ((uintptr_t)origin & 3) == 0, "%s: the origin is two aligned int32 words on the device (y0, x0)", name);
+        if (int rc = roi_window_ok(name, p->H, p->W, p->h, p->w)) return rc;
+    } else if (int rc = roi_window_at_ok(name, p->H, p->W, p->y0, p->x0, p->h, p->w)) {
+        return rc;
+    }
+    OTVM_REQUIRE(p->win_alpha && p->win_trimap, "%s: null window alpha or window trimap", name);
+    OTVM_REQUIRE(p->alpha || p->alpha_u8 || p->trimap || p->fgr, "%s: no output requested", name);
+    OTVM_REQUIRE(!p->fgr || (p->win_fgr && p->frame), "%s: fgr needs the window's F planes and the frame", name);
     OTVM_REQUIRE((((uintptr_t)p->win_alpha | (uintptr_t)p->win_trimap | (uintptr_t)p->win_fgr | (uintptr_t)p->outside | (uintptr_t)p->alpha |
-                   (uintptr_t)p->trimap | (uintptr_t)p->fgr) & 3) == 0, "otvm_roi_paste: misaligned fp32 plane");
+                   (uintptr_t)p->trimap | (uintptr_t)p->fgr) & 3) == 0, "%s: misaligned fp32 plane", name);
     const bool vec = p->W % 4 == 0 && (((uintptr_t)p->outside | (uintptr_t)p->alpha | (uintptr_t)p->trimap | (uintptr_t)p->fgr) & 15) == 0 &&
                      (((uintptr_t)p->alpha_u8 | (uintptr_t)p->frame) & 3) == 0;
     const dim3 grid(roi_blocks(p->H, p->W));
-    if (vec) hipLaunchKernelGGL(roi_paste_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, *p);
-    else hipLaunchKernelGGL(roi_paste_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, *p);
-    OTVM_CHECK_LAUNCH("otvm_roi_paste");
+    hipStream_t s = (hipStream_t)stream;
+    if (at) {
+        if (vec) hipLaunchKernelGGL((roi_paste_kernel<true, true>), grid, dim3(256), 0, s, *p, origin);
+        else hipLaunchKernelGGL((roi_paste_kernel<false, true>), grid, dim3(256), 0, s, *p, origin);
+    } else {
+        if (vec) hipLaunchKernelGGL((roi_paste_kernel<true, false>), grid, dim3(256), 0, s, *p, nullptr);
+        else hipLaunchKernelGGL((roi_paste_kernel<false, false>), grid, dim3(256), 0, s, *p, nullptr);
+    }
+    OTVM_CHECK_LAUNCH(name);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int otvm_roi_crop(const otvm_roi_crop_params* p, void* stream) { return roi_crop_checked("otvm_roi_crop", p, nullptr, false, stream); }
+
+extern "C" int otvm_roi_paste(const otvm_roi_paste_params* p, void* stream) { return roi_paste_checked("otvm_roi_paste", p, nullptr, false, stream); }
+
+extern "C" int otvm_roi_crop_at(const otvm_roi_crop_params* p, const int32_t* origin, void* stream) {
+    return roi_crop_checked("otvm_roi_crop_at", p, origin, true, stream);
+}
+
+extern "C" int otvm_roi_paste_at(const otvm_roi_paste_params* p, const int32_t* origin, void* stream) {
+    return roi_paste_checked("otvm_roi_paste_at", p, origin, true, stream);
+}
+
+extern "C" int otvm_roi_track(const otvm_roi_track_params* p, void* stream) {
+    OTVM_REQUIRE(p && p->box && p->out, "otvm_roi_track: null pointer (params, box or out)");
+    if (int rc = roi_window_ok("otvm_roi_track", p->H, p->W, p->h, p->w)) return rc;
+    OTVM_REQUIRE(p->hold >= 1 && p->hold <= ROI_MAX_SIDE, "otvm_roi_track: hold is 1 .. 16383 pixels, got %d", p->hold);
+    OTVM_REQUIRE((((uintptr_t)p->box | (uintptr_t)p->prev | (uintptr_t)p->out) & 3) == 0, "otvm_roi_track: misaligned box, prev or out");
+    hipLaunchKernelGGL(roi_track_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, p->box, p->prev, p->out, p->H, p->W, p->h, p->w, p->hold);
+    OTVM_CHECK_LAUNCH("otvm_roi_track");
     return 0;
 }

@@ -37,7 +37,7 @@ and the change of alpha at which it lets go, --stabilise-region unknown|all wher
 checkpoint here, the filter is checked by definition and by property on synthetic clips, not by quality on real footage.  Works
 with --masks, --keyframes (forward-only schedules), --work-scale, --fgr and --composite; refused with --viz, --batch > 1 and
 without --demo.  The summary carries stabilise.
---roi auto|Y0,X0,H,W [--roi-margin M] (demo layout): region-of-interest matting -- the network runs in a window round the subject
+--roi auto|track[,H,W]|Y0,X0,H,W [--roi-margin M] (demo layout): region-of-interest matting -- the network runs in a window round the subject
 and alpha (with --fgr / --composite also the foreground) is pasted back into the frame (video.run_video_matte(roi=...),
 otvm_amd/roi.py).  auto with --masks frame tracks the mask's unknown band frame by frame; auto otherwise places ONE window round
 the classes other than background of the clip's trimaps / masks / label maps, which the subject must not leave (roi_clipped in the
@@ -46,6 +46,11 @@ the full-frame matte (the network's global context is the window's), it is check
 (32) is a PLACEHOLDER.  Works with --masks, --keyframes, --fgr, --composite and --stabilise; refused with --work-scale, --viz,
 --batch > 1 and without --demo.  The summary carries roi, roi_margin and per clip roi_size and roi_clipped.  Between clips whose
 window size differs the engine's frame plans are dropped (nothing else evicts them).
+--roi track[,H,W] (trimap / --masks key / --keyframes clips): the TRACKING window -- one size for the clip (H,W, or the largest
+source's box plus the margin), an origin per frame that lives on the device and follows the box of the trimap the network put out
+for the neighbouring frame (otvm_roi_track; roi.track_origin is the policy), so the window lags ONE frame: a subject that moves more
+than max(1, margin // 2) pixels a frame, or outgrows the size, is cut, and roi_clipped lists those frames.  Nothing is read back
+inside the frame loop.  The same exclusions as --roi auto, and refused with --masks frame (auto tracks there).
 Frame IO runs through otvm_amd/io_pipeline.py: the demo flow decodes ahead in a thread pool and uploads on a copy
 stream, both flows download the 8-bit alphas asynchronously and PNG-encode them in a pool (the reference's loop blocks
 on .cpu() + cv2.imwrite per frame, eval.py:209-217).
@@ -122,17 +127,22 @@ def parse_stabilise_options(strength, taus, region):
 
 
 def parse_roi_options(roi, margin):
-    """--roi "auto" | "Y0,X0,H,W", --roi-margin M -> run_video_matte's (roi, roi_margin); (None, 32) when --roi was not given."""
+    """--roi "auto" | "track[,H,W]" | "Y0,X0,H,W", --roi-margin M -> run_video_matte's (roi, roi_margin); (None, 32) when --roi was not given."""
     if roi is None:
         if margin is not None:
             raise SystemExit("eval_cli: --roi-margin belongs to --roi")
         return None, 32
     if margin is not None and margin < 0:
         raise SystemExit("eval_cli: --roi-margin is a number of pixels >= 0, got %d" % margin)
-    if roi != "auto":
+    if roi == "track" or roi.startswith("track,"):
+        parts = roi.split(",")[1:]
+        if parts and (len(parts) != 2 or not all(x.strip().isdigit() and int(x) >= 1 for x in parts)):
+            raise SystemExit("eval_cli: --roi track takes no size or one, track,H,W (pixels, H and W at least 1), got %r" % roi)
+        roi = ("track",) + tuple(int(x) for x in parts) if parts else "track"
+    elif roi != "auto":
         parts = roi.split(",")
         if len(parts) != 4 or not all(x.strip().isdigit() for x in parts) or int(parts[2]) < 1 or int(parts[3]) < 1:
-            raise SystemExit("eval_cli: --roi is auto or a window Y0,X0,H,W (pixels, H and W at least 1), got %r" % roi)
+            raise SystemExit("eval_cli: --roi is auto, track[,H,W] or a window Y0,X0,H,W (pixels, H and W at least 1), got %r" % roi)
         roi = tuple(int(x) for x in parts)
     return roi, 32 if margin is None else margin
 
@@ -168,9 +178,10 @@ def main(argv=None):
                          "(default 24,0.5: placeholders)")
     ap.add_argument("--stabilise-region", default=None, choices=["unknown", "all"],
                     help="--stabilise: filter only the trimap's unknown class (default) or every pixel")
-    ap.add_argument("--roi", default=None, metavar="auto|Y0,X0,H,W",
+    ap.add_argument("--roi", default=None, metavar="auto|track[,H,W]|Y0,X0,H,W",
                     help="demo layout: run the network in a window round the subject and paste the result back (the matte of the "
-                         "cropped clip, not the full-frame matte); auto places the window from the trimaps / masks")
+                         "cropped clip, not the full-frame matte); auto places the window from the trimaps / masks, track lets it "
+                         "follow the propagated trimap, one frame behind")
     ap.add_argument("--roi-margin", type=int, default=None, metavar="M",
                     help="--roi auto: pixels kept round the subject's box (default 32: a placeholder, not tuned on real footage)")
     ap.add_argument("--max-frames", type=int, default=None, help="only the first N frames of every sequence")
@@ -226,6 +237,9 @@ def main(argv=None):
         raise SystemExit("eval_cli: --roi and --work-scale exclude each other (a window at the working resolution is out of scope)")
     if args.masks and not args.demo:
         raise SystemExit("eval_cli: --masks reads the demo layout's mask/ folder; add --demo")
+    if args.masks == "frame" and roi is not None and (roi == "track" or roi[0] == "track"):
+        raise SystemExit("eval_cli: --roi track follows a propagated trimap; --masks frame propagates nothing, and --roi auto already "
+                         "tracks there")
     if args.masks and args.batch is not None and args.batch > 1:
         raise SystemExit("eval_cli: --batch %d steps clips in lock-step through matte_batch, which does not implement --masks"
                          % args.batch)
@@ -486,7 +500,7 @@ def main(argv=None):
         summary["mask_band"] = list(mask_band) if isinstance(mask_band, tuple) else [dk if mask_band is None else mask_band] * 2
         summary["mask_thresholds"] = [mask_lo, mask_hi]
     if roi is not None:
-        summary["roi"], summary["roi_margin"] = (roi if roi == "auto" else list(roi)), roi_margin
+        summary["roi"], summary["roi_margin"] = (roi if isinstance(roi, str) else list(roi)), roi_margin
         summary["roi_size"] = {seqs[i]["name"]: o["roi_size"] for i, o in summary["outputs"].items() if o.get("roi_size")}
         summary["roi_clipped"] = {seqs[i]["name"]: o["roi_clipped"] for i, o in summary["outputs"].items() if "roi_clipped" in o}
     if stabilise is not None:

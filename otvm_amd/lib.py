@@ -119,6 +119,10 @@ class RoiPasteParams(C.Structure):
                 ("alpha", vp), ("alpha_u8", vp), ("trimap", vp), ("fgr", vp)]
 
 
+class RoiTrackParams(C.Structure):
+    _fields_ = [("box", vp), ("prev", vp), ("out", vp), ("H", i32), ("W", i32), ("h", i32), ("w", i32), ("hold", i32)]
+
+
 class PpmHeadParams(C.Structure):
     _fields_ = [("pooled", vp), ("C", i32), ("K_pad", i32), ("Cout", i32),
                 ("w", vp * 4), ("bias", vp * 4), ("gamma", vp * 4), ("beta", vp * 4), ("out", vp * 4),
@@ -199,6 +203,9 @@ _PROTOS = {
     "otvm_trimap_bbox": (i32, [C.POINTER(RoiBboxParams), vp]),
     "otvm_roi_crop": (i32, [C.POINTER(RoiCropParams), vp]),
     "otvm_roi_paste": (i32, [C.POINTER(RoiPasteParams), vp]),
+    "otvm_roi_track": (i32, [C.POINTER(RoiTrackParams), vp]),
+    "otvm_roi_crop_at": (i32, [C.POINTER(RoiCropParams), vp, vp]),
+    "otvm_roi_paste_at": (i32, [C.POINTER(RoiPasteParams), vp, vp]),
     "otvm_gn_stats_b": (i32, [vp, i64, i32, i32, vp, i32, i64, i32, vp]),
     "otvm_gn_table_b": (i32, [vp, i64, i32, vp, vp, vp, vp, i32, i32, i32, vp]),
     "otvm_gn_apply_b": (i32, [C.POINTER(GnApplyParams), vp]),

@@ -4,7 +4,10 @@ there is no PyTorch fallback.
 
 Checked by definition only: the result of a window is, bit for bit, the matte of the cropped clip pasted back.  It is NOT the
 full-frame result (the decoder's pyramid pooling sees the window, not the frame), and the default margin is a PLACEHOLDER: nobody
-has tuned it on real footage."""
+has tuned it on real footage.
+
+The tracking window (run_video_matte(roi="track")): otvm_roi_track, otvm_roi_crop_at and otvm_roi_paste_at keep the window's origin
+on the device, a row of an int32 log per frame; track_origin is the same policy on the host, and rows_of the one read-back."""
 import ctypes as C
 
 import torch
@@ -74,6 +77,31 @@ def touched_sides(window, box, H, W):
             or (box[3] >= x0 + w - 1 and x0 + w < W))
 
 
+def hold_of(margin):
+    """The pixels a tracked box keeps from a window side before the window moves: max(1, margin // 2).  At least 1: the box is
+    measured inside the window, so it can touch a side but never cross it.  (A PLACEHOLDER like the margin itself.)"""
+    return max(1, int(margin) // 2)
+
+
+def track_origin(box, prev, h, w, H, W, hold):
+    """(oy, ox) of the h x w tracking window of a frame, from its already-matted temporal neighbour: ``box`` is the non-background
+    box of the neighbour's output trimap in FRAME coordinates, ``prev`` the neighbour's origin.  Each axis on its own HOLDS
+    ``prev`` while the box keeps at least ``hold`` pixels from both window sides on that axis (a window side that is the frame's
+    side always counts as held), and recentres on the box, clamped to the frame, otherwise; an empty box holds both.
+    ``prev`` None: a step with a trimap of its own -- window_origin(box), (0, 0) for an empty box.  Pure integer arithmetic;
+    otvm_roi_track (csrc/roi.hip) is the same policy on the device, where the box comes in window coordinates."""
+    if prev is None:
+        return window_origin(box, h, w, H, W)
+    if is_empty(box):
+        return tuple(prev)
+    out = []
+    for a, (side, full) in enumerate(((h, H), (w, W))):
+        o, lo, hi = prev[a], box[a], box[a + 2]
+        held = (lo - o >= hold or o == 0) and (o + side - 1 - hi >= hold or o + side == full)
+        out.append(o if held else min(max((lo + hi + 1) // 2 - side // 2, 0), full - side))
+    return tuple(out)
+
+
 def check_window(window, H, W, who="otvm_amd.roi"):
     """(y0, x0, h, w) as four ints, refused when it is empty or leaves the H x W frame."""
     try:
@@ -119,15 +147,61 @@ def trimap_bbox(src, out=None):
     return out
 
 
+def rows_of(buf):
+    """A device int32 [n,k] buffer as n host tuples: THE read-back of the tracking window -- the source boxes before the first
+    frame, the origin log and the output boxes after the last -- and nothing in between."""
+    return [tuple(r) for r in buf.cpu().view(buf.shape[0], -1).tolist()]
+
+
+def check_size(size, H, W, who="otvm_amd.roi"):
+    """(h, w) as two ints, refused unless 1 <= h <= H and 1 <= w <= W."""
+    try:
+        h, w = (int(v) for v in size)
+        ok = all(int(v) == v and not isinstance(v, bool) for v in size)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("%s: a window size is two integers (h, w), got %r" % (who, size))
+    if not (1 <= h <= H and 1 <= w <= W):
+        raise ValueError("%s: the window size (h, w) = %r needs 1 <= h <= %d and 1 <= w <= %d (the %dx%d frame)" % (who, (h, w), H, W, H, W))
+    return h, w
+
+
+def _origin_row(origin, dev, who, words=2):
+    if (not torch.is_tensor(origin) or origin.dtype != torch.int32 or origin.numel() != words or not origin.is_contiguous()
+            or origin.device != dev):
+        raise ValueError("otvm_amd.roi: %s takes %d contiguous int32 on %s" % (who, words, dev))
+
+
+def track(box, prev, out, size, H, W, hold):
+    """otvm_roi_track: ``out`` (row t of the int32 [T,2] origin log) = track_origin of the neighbour's ``box`` row (the int32 [8]
+    trimap_bbox wrote, in the neighbour's window) and the neighbour's origin ``prev`` (its row of the log); ``prev`` None: centred
+    on ``box``, which is then in frame coordinates (a step with a trimap of its own).  One small launch on the current stream;
+    nothing is synchronised."""
+    dev = out.device
+    _origin_row(box, dev, "track's box", 8)
+    _origin_row(out, dev, "track's out")
+    if prev is not None:
+        _origin_row(prev, dev, "track's prev")
+    h, w = check_size(size, H, W)
+    if isinstance(hold, bool) or int(hold) != hold or hold < 1:
+        raise ValueError("otvm_amd.roi: hold is a number of pixels >= 1 (an integer), got %r" % (hold,))
+    p = L.RoiTrackParams()
+    p.box, p.prev, p.out = box.data_ptr(), None if prev is None else prev.data_ptr(), out.data_ptr()
+    p.H, p.W, p.h, p.w, p.hold = H, W, h, w, int(hold)
+    L.check(L.load().otvm_roi_track(C.byref(p), _stream(dev)), "roi_track")
+    return out
+
+
 def boxes_of(rows):
     """A read-back [T,8] buffer (or one row) as host tuples: ([unknown box per row], [non-bg box per row])."""
     rows = rows.cpu().view(-1, 8).tolist()
     return [tuple(r[:4]) for r in rows], [tuple(r[4:]) for r in rows]
 
 
-def crop(window, frame=None, trimap=None, labels=None):
+def crop(window, frame=None, trimap=None, labels=None, origin=None):
     """The window (y0, x0, h, w) of whichever of frame uint8 [H,W,3], trimap float [3,H,W] and labels uint8 [H,W] are given, in
-    ONE launch: (frame, trimap, labels) with None where nothing was given."""
+    ONE launch: (frame, trimap, labels) with None where nothing was given.  (``origin``: crop_at's, ``window`` then being (h, w).)"""
     given = [x for x in (frame, trimap, labels) if x is not None]
     if not given:
         raise ValueError("otvm_amd.roi: crop needs a frame, a trimap or a label map")
@@ -142,7 +216,11 @@ def crop(window, frame=None, trimap=None, labels=None):
     if len(sizes) != 1 or any(not x.is_cuda or x.device != dev for x in given):
         raise ValueError("otvm_amd.roi: crop takes tensors of one resolution on one GPU, got %s" % sorted(sizes))
     (H, W), = sizes
-    y0, x0, h, w = check_window(window, H, W)
+    if origin is None:
+        y0, x0, h, w = check_window(window, H, W)
+    else:
+        (y0, x0), (h, w) = (0, 0), check_size(window, H, W)
+        _origin_row(origin, dev, "crop_at")
     p = L.RoiCropParams()
     p.H, p.W, p.y0, p.x0, p.h, p.w = H, W, y0, x0, h, w
     out = [None, None, None]
@@ -154,17 +232,31 @@ def crop(window, frame=None, trimap=None, labels=None):
             out[j] = torch.empty(shape, dtype=x.dtype, device=dev)
             setattr(p, name, x.data_ptr())
             setattr(p, name + "_out", out[j].data_ptr())
-    L.check(L.load().otvm_roi_crop(C.byref(p), _stream(dev)), "roi_crop")
+    if origin is None:
+        L.check(L.load().otvm_roi_crop(C.byref(p), _stream(dev)), "roi_crop")
+    else:
+        L.check(L.load().otvm_roi_crop_at(C.byref(p), origin.data_ptr(), _stream(dev)), "roi_crop_at")
     return tuple(out)
 
 
-def paste(window, H, W, alpha, trimap, fgr=None, frame=None, rgb=False, outside=None, want=("alpha", "alpha_u8", "trimap", "fgr")):
+def crop_at(origin, size, frame=None, trimap=None, labels=None):
+    """crop() of the (h, w) = ``size`` window whose origin the KERNEL reads from ``origin``, two int32 on the device (a row of the
+    [T,2] log track() writes) -- clamped there to [0, H - h] x [0, W - w] whatever the row holds.  Nothing is synchronised."""
+    return crop(size, frame, trimap, labels, origin=origin)
+
+
+def paste(window, H, W, alpha, trimap, fgr=None, frame=None, rgb=False, outside=None, want=("alpha", "alpha_u8", "trimap", "fgr"),
+          origin=None):
     """A window's results back at H x W in one pass.  alpha [h,w], trimap [3,h,w], fgr [3,h,w] (R, G, B; optional) are the
     window's; ``frame`` uint8 [H,W,3] gives F outside the window, ``outside`` (one-hot [3,H,W] or None = background) the trimap
     and alpha there.  Returns (alpha [H,W], alpha_u8 [H,W], trimap [3,H,W], fgr [3,H,W]), None for what ``want`` leaves out or
-    (fgr) what has no source."""
+    (fgr) what has no source.  (``origin``: paste_at's, ``window`` then being (h, w).)"""
     dev = alpha.device
-    y0, x0, h, w = check_window(window, H, W)
+    if origin is None:
+        y0, x0, h, w = check_window(window, H, W)
+    else:
+        (y0, x0), (h, w) = (0, 0), check_size(window, H, W)
+        _origin_row(origin, dev, "paste_at")
     alpha, trimap = alpha.contiguous(), trimap.contiguous()
     if tuple(alpha.shape) != (h, w) or tuple(trimap.shape) != (3, h, w) or alpha.dtype != torch.float32 or trimap.dtype != torch.float32:
         raise ValueError("otvm_amd.roi: paste takes the window's fp32 alpha [%d,%d] and trimap [3,%d,%d], got %s and %s"
@@ -195,5 +287,13 @@ def paste(window, H, W, alpha, trimap, fgr=None, frame=None, rgb=False, outside=
         if name in want and (name != "fgr" or with_fgr):
             res[name] = torch.empty(shape, dtype=dt, device=dev)
             setattr(p, name, res[name].data_ptr())
-    L.check(L.load().otvm_roi_paste(C.byref(p), _stream(dev)), "roi_paste")
+    if origin is None:
+        L.check(L.load().otvm_roi_paste(C.byref(p), _stream(dev)), "roi_paste")
+    else:
+        L.check(L.load().otvm_roi_paste_at(C.byref(p), origin.data_ptr(), _stream(dev)), "roi_paste_at")
     return res.get("alpha"), res.get("alpha_u8"), res.get("trimap"), res.get("fgr")
+
+
+def paste_at(origin, size, H, W, alpha, trimap, fgr=None, frame=None, rgb=False, outside=None, want=("alpha", "alpha_u8", "trimap", "fgr")):
+    """paste() of the (h, w) = ``size`` window whose origin the KERNEL reads from ``origin`` (as crop_at)."""
+    return paste(size, H, W, alpha, trimap, fgr, frame, rgb, outside, want, origin=origin)

@@ -147,7 +147,7 @@ class _ClipPlan:
         self.roi, self.region = None, None                # the checked (window or "auto", margin); run_video_matte's _RegionOfInterest
         if roi is not None:
             # (host only, like everything here: the window itself is placed by upload(), which has the sources on the device)
-            self.roi = _RegionOfInterest.refuse(roi, roi_margin, frames, alphas, backgrounds, work_scale)
+            self.roi = _RegionOfInterest.refuse(roi, roi_margin, frames, alphas, backgrounds, work_scale, masks)
         if work_scale is not None:
             if work_scale not in guided.SCALES:
                 raise ValueError("run_video_matte: work_scale is 2, 3 or 4 (an integer scale), got %r" % (work_scale,))
@@ -231,8 +231,8 @@ class _ClipPlan:
             h, w = np.shape(keyframes[self.k0])[-2:]
             if work_scale is not None:
                 h, w = guided.work_size(h, w, work_scale)
-            if self.roi is not None and self.roi[0] != "auto":
-                h, w = self.roi[0][2:]                    # (roi="auto": upload() places the window and schedules again)
+            if self.roi is not None and isinstance(self.roi[0], tuple) and len(self.roi[0]) in (3, 4):
+                h, w = self.roi[0][-2:]                   # (roi="auto" / "track": upload() sizes the window and schedules again)
             self._schedule(h, w)
         else:
             self.steps = [(i, "frame", i == 0, i == T - 1, None) for i in range(T)]  # alpha flow: eval.py's loop as it is
@@ -297,6 +297,12 @@ class _ClipPlan:
         rows = torch.empty((len(order), 8), dtype=torch.int32, device=dev)
         for j, t in enumerate(order):
             _roi.trimap_bbox(on_dev[t], rows[j])
+        if self.region.follows:
+            # the tracking window: the same read-back decides the SIZE only; the sources stay at H x W on the device and each is
+            # cropped at its own step, where the window then is (region.stage fills self.tri / self.lab)
+            self.region.place_track(on_dev, dict(zip(order, rows)), {t: r[4:] for t, r in zip(order, _roi.rows_of(rows))}, H, W, self.T)
+            self._schedule(*self.region.size)
+            return {}
         self.region.place_static(dict(zip(order, _roi.boxes_of(rows)[1])), H, W, self.T)
         win = self.region.window(0)
         self._schedule(win[2], win[3])
@@ -410,7 +416,11 @@ class _RegionOfInterest:
     anything is uploaded; the windows are placed by _ClipPlan.upload(), which holds the sources:
       place_tracking : ``masks``: one size for the clip (one engine plan), an origin per frame from the frame's unknown box;
                        outside the window alpha follows the frame's own trimap
-      place_static   : every other route: one window for the clip; outside it is background, and nothing there is looked at"""
+      place_static   : every other route: one window for the clip; outside it is background, and nothing there is looked at
+      place_track    : roi="track" on those routes: one size for the clip, an origin per frame that lives ON THE DEVICE (a row of an
+                       int32 log, otvm_roi_track): a step with a trimap of its own centres on it, every other step follows the
+                       box of the output trimap of its already-matted temporal neighbour (roi.track_origin), one frame behind.
+                       Sources are cropped per step, with the frame; nothing is read back between the first and the last frame"""
 
     def __init__(self, plan, foreground, frames_are_rgb, new_background):
         self.spec, self.margin = plan.roi
@@ -419,13 +429,24 @@ class _RegionOfInterest:
         self.windows, self.HW, self.tracking = None, None, False
         self.full = self.outside = self.tri = self.fgr_full = None
         self.rows, self.seen = None, []                   # static: [T,8] boxes of the output trimaps, in window coordinates
+        self.follows = isinstance(self.spec, tuple) and self.spec[0] == "track"     # place_track's mode
+        self.track_size, self.log, self.sources, self.source_rows = None, None, {}, {}
 
     @staticmethod
-    def refuse(spec, margin, frames, alphas, backgrounds, work_scale):
-        """-> (the window as four ints or "auto", the margin)"""
-        if isinstance(spec, str):
+    def refuse(spec, margin, frames, alphas, backgrounds, work_scale, masks=None):
+        """-> (the window as four ints, "auto", or ("track",) / ("track", h, w); the margin)"""
+        track = spec == "track" if isinstance(spec, str) else (isinstance(spec, (tuple, list)) and len(spec) == 3 and spec[0] == "track")
+        if track:
+            if not isinstance(spec, str):
+                if not all(not isinstance(v, bool) and isinstance(v, (int, np.integer)) for v in spec[1:]) or spec[1] < 1 or spec[2] < 1:
+                    raise ValueError("run_video_matte: roi = ('track', h, w) needs integers h, w >= 1, got %r" % (spec,))
+            spec = ("track",) + (() if isinstance(spec, str) else (int(spec[1]), int(spec[2])))
+            if masks is not None:
+                raise ValueError("run_video_matte: roi='track' follows a PROPAGATED trimap; `masks` mattes every frame from its own "
+                                 "mask, and roi='auto' already tracks there")
+        elif isinstance(spec, str):
             if spec != "auto":
-                raise ValueError("run_video_matte: roi is None, 'auto' or a window (y0, x0, h, w), got %r" % (spec,))
+                raise ValueError("run_video_matte: roi is None, 'auto', 'track' or a window (y0, x0, h, w), got %r" % (spec,))
         else:
             try:
                 ok = len(spec) == 4 and all(not isinstance(v, bool) and int(v) == v for v in spec)
@@ -451,7 +472,9 @@ class _RegionOfInterest:
             if f0.dtype != torch.uint8:
                 raise ValueError("run_video_matte: roi takes uint8 [H,W,3] frames (float frames have no region-of-interest "
                                  "route), got %s" % f0.dtype)
-            if not isinstance(spec, str):
+            if track and len(spec) == 3:
+                _roi.check_size(spec[1:], f0.shape[0], f0.shape[1], "run_video_matte: roi")
+            elif not track and not isinstance(spec, str):
                 _roi.check_window(spec, f0.shape[0], f0.shape[1], "run_video_matte: roi")
         return spec, int(margin)
 
@@ -487,11 +510,32 @@ class _RegionOfInterest:
                                      % (win, t, box[0], box[2], box[1], box[3]))
         self.windows = [win] * T
 
+    def place_track(self, sources, source_rows, nonbg, H, W, T):
+        """sources: {frame: the trimap / label map at H x W on the device}; source_rows: {frame: its int32 [8] box row on the
+        device}; nonbg: {frame: its non-background box on the host} -- which decides the SIZE, and only that"""
+        self.HW, self.sources, self.source_rows = (H, W), sources, source_rows
+        if len(self.spec) == 3:
+            h, w = _roi.check_size(self.spec[1:], H, W, "run_video_matte: roi")
+            for t, box in sorted(nonbg.items()):
+                if not _roi.is_empty(box) and (box[2] - box[0] + 1 > h or box[3] - box[1] + 1 > w):
+                    raise ValueError("run_video_matte: the %dx%d window of roi = %r does not hold the trimap / label map of frame %d "
+                                     "(its classes other than background: rows %d ... %d, columns %d ... %d)"
+                                     % (h, w, self.spec, t, box[0], box[2], box[1], box[3]))
+        else:
+            h, w = _roi.window_size(list(nonbg.values()), H, W, self.margin)
+        self.track_size, self.hold = (h, w), _roi.hold_of(self.margin)
+        dev = next(iter(source_rows.values())).device
+        # per frame: words 0 .. 7 the boxes of the output trimap (in the frame's window), words 8, 9 the window's origin -- ONE
+        # buffer, so that result() reads the clip back with one copy.  Rows start as the empty box at (0, 0).
+        self.log = torch.tensor([h, w, -1, -1, h, w, -1, -1, 0, 0], dtype=torch.int32, device=dev).repeat(T, 1)
+
     def window(self, i):
         return self.windows[i]
 
     @property
     def size(self):
+        if self.follows:
+            return self.track_size
         return None if not self.windows else tuple(self.windows[0][2:])
 
     def stage(self, f, i, dev):
@@ -507,6 +551,8 @@ class _RegionOfInterest:
         self.full = f.to(dev, non_blocking=True).contiguous()
         if ready is not None:
             torch.cuda.current_stream(dev).wait_event(ready)
+        if self.follows:
+            return self._stage_track(i, dev)
         win = self.windows[i]
         if self.tracking:
             # this frame's own trimap, at H x W: what the paste shows outside the window; nothing of it outlives the step
@@ -516,6 +562,27 @@ class _RegionOfInterest:
             fg = _roi.crop(win, frame=self.full)[0]
         return fg, fg, win[2], win[3], True, None, None
 
+    def _stage_track(self, i, dev):
+        """The tracking window's stage: the launch that decides row ``i`` of the origin log, then ONE crop at that row of the
+        frame and, in the same launch, of the step's trimap or label map (which _ClipPlan.inputs then finds cropped)."""
+        plan, (H, W) = self.plan, self.HW
+        kind = plan.kinds.get(i, "frame")
+        if kind == "key":
+            # a trimap of its own: centred on it (its box is in frame coordinates, there is no neighbour to start from)
+            _roi.track(self.source_rows[i], None, self.log[i, 8:], self.track_size, H, W, self.hold)
+        else:
+            # the already-matted temporal neighbour on the side the sweep comes from (not the schedule's predecessor)
+            n = i - 1 if i > plan.k0 else i + 1
+            _roi.track(self.log[n, :8], self.log[n, 8:], self.log[i, 8:], self.track_size, H, W, self.hold)
+        src = self.sources.get(i)
+        fg, tri, lab = _roi.crop_at(self.log[i, 8:], self.track_size, frame=self.full, trimap=src if kind == "key" else None,
+                                    labels=src if kind == "labels" else None)
+        if kind == "key":
+            plan.tri[i] = tri[None, None]
+        elif kind == "labels":
+            plan.lab[i] = lab
+        return fg, fg, self.track_size[0], self.track_size[1], True, None, None
+
     def take_trimap(self):
         tri, self.tri = self.tri, None
         return tri
@@ -524,6 +591,15 @@ class _RegionOfInterest:
         """(alpha, alpha_u8, trimap) at H x W; with ``foreground`` the pasted F is kept for foreground_bytes().  A static window
         also files the box of the frame's output trimap, for roi_clipped."""
         tri = out[1][0, 0].contiguous()
+        if self.follows:
+            _roi.trimap_bbox(tri, self.log[i, :8])        # what the next frame's window follows, and roi_clipped's box
+            self.seen.append(i)
+            self.plan.lab.pop(i, None)
+            alpha, u8, trimap, self.fgr_full = _roi.paste_at(
+                self.log[i, 8:], self.track_size, self.HW[0], self.HW[1], out[3][0, 0, 0], tri,
+                engine.last_fgr if self.foreground else None, self.full, self.rgb, None,
+                ("alpha", "alpha_u8", "trimap") + (("fgr",) if self.foreground else ()))
+            return alpha, u8, trimap
         if not self.tracking:
             if self.rows is None:
                 self.rows = torch.empty((len(self.windows), 8), dtype=torch.int32, device=dev)
@@ -545,6 +621,17 @@ class _RegionOfInterest:
     def result(self):
         """roi, roi_size and roi_clipped (ONE read-back of the boxes, after the last frame)"""
         clipped = []
+        if self.follows:
+            if self.log is None:
+                return dict(roi=[], roi_size=None, roi_clipped=[])
+            (H, W), (h, w) = self.HW, self.track_size
+            rows = _roi.rows_of(self.log)
+            self.windows = [(r[8], r[9], h, w) for r in rows]
+            for i in sorted(self.seen):
+                y0, x0, b = rows[i][8], rows[i][9], rows[i][4:8]
+                if not _roi.is_empty(b) and _roi.touched_sides(self.windows[i], (b[0] + y0, b[1] + x0, b[2] + y0, b[3] + x0), H, W):
+                    clipped.append(i)
+            return dict(roi=list(self.windows), roi_size=self.size, roi_clipped=clipped)
         if self.rows is not None:
             H, W = self.HW
             boxes = _roi.boxes_of(self.rows)[1]
@@ -706,7 +793,8 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                   property on synthetic clips, not by quality on real footage, and the default parameters are PLACEHOLDERS.
                   Refused for float frames, with ``backgrounds`` and for a keyframe schedule that is not in natural order (a
                   backward sweep); not available in run_video_matte_batch.
-    roi         : None (off: a frame issues exactly the launches it issues without the option), "auto" or a window (y0, x0, h, w):
+    roi         : None (off: a frame issues exactly the launches it issues without the option), "auto", a window (y0, x0, h, w),
+                  "track" or ("track", h, w):
                   region-of-interest matting.  Every frame (uint8 [H,W,3] only) is cropped on the device to an h x w window, the
                   network runs there -- the memory schedule, large-input rule included, is evaluated at h x w -- and alpha, the
                   trimap (with ``foreground`` also F) are pasted back into H x W (otvm_amd/roi.py).  Checked BY DEFINITION ONLY:
@@ -727,7 +815,20 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                   roi_size=(h, w) and roi_clipped.  Every window size is an engine plan of its own and NOTHING is evicted here: a
                   process that mattes many clips drops them itself (EvalModel.drop_plans).  Refused for float frames, the
                   ``alphas`` flow, ``backgrounds`` and together with ``work_scale``; not available in run_video_matte_batch.
-    roi_margin  : pixels kept round the box on every side by roi="auto" (default 32: a PLACEHOLDER nobody tuned on real footage)
+                  "track" or ("track", h, w) with ``trimap`` / ``mask`` / ``keyframes``: the TRACKING window.  One size for the
+                  clip (one engine plan) -- h x w as given, refused when a source's classes other than background do not fit; or
+                  the largest source's box (not the union) plus ``roi_margin`` on every side, rounded up to a multiple of 32 -- and
+                  an origin per frame that lives ON THE DEVICE (a row of an int32 log; otvm_roi_track): a step with a trimap of its
+                  own (the first frame, full keyframes) is centred on it, every other step starts from its already-matted
+                  temporal neighbour (t-1 in the forward sweep, t+1 in the backward one) and, per axis, HOLDS that origin while
+                  the non-background box of the trimap returned for that frame keeps hold = max(1, roi_margin // 2) pixels from
+                  both window sides (a side that is the frame's counts as held), and recentres on the box otherwise
+                  (roi.track_origin).  Nothing is read back inside the frame loop: the sources' boxes once before the first frame,
+                  the origins and the output boxes once after the last.  The window LAGS ONE FRAME: a subject that moves more than
+                  ``hold`` pixels a frame, or outgrows the size, is cut -- roi_clipped lists those frames.  Outside the window
+                  everything is background.  Checked by definition only, as above; refused with ``masks`` ("auto" tracks there).
+    roi_margin  : pixels kept round the box on every side by roi="auto" / "track", and twice the pixels a tracked box keeps from a
+                  window side before the window moves (default 32: a PLACEHOLDER nobody tuned on real footage)
     Returns dict(alpha=[T,H,W] float32, alpha_u8=[T,H,W] uint8 (truncated, eval.py:209), trimap=[T,3,H,W],
     bank_frames=[per frame: ids of the frames resident in the memory bank after that frame's update]) and, when ``keyframes``
     was given, anchor_frames=[per frame: those of them that are anchors], schedule=[the steps issued, keyframe_schedule's tuples].
