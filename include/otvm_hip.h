@@ -77,7 +77,9 @@ const char* otvm_last_error(void);
                                   otvm_roi_bbox_params, otvm_roi_crop_params and otvm_roi_paste_params;
                                   likewise the tracking window of region-of-interest matting: otvm_roi_track with
                                   otvm_roi_track_params, and otvm_roi_crop_at / otvm_roi_paste_at, which take the two structs above
-                                  as they are plus a device pointer) */
+                                  as they are plus a device pointer;
+                                  likewise multi-subject matting: otvm_subjects_track, otvm_subjects_crop, otvm_subjects_bbox and
+                                  otvm_subjects_resolve with their otvm_subjects_*_params) */
 int otvm_abi_version(void);
 
 /* ---------------------------------------------------------------- weights (load time) ----------
@@ -769,6 +771,85 @@ int otvm_roi_track(const otvm_roi_track_params* p, void* stream);
  * 1 <= h <= H and 1 <= w <= W; every other refusal as in the forms above.  The kernel bodies are those of the forms above.   */
 int otvm_roi_crop_at(const otvm_roi_crop_params* p, const int32_t* origin, void* stream);
 int otvm_roi_paste_at(const otvm_roi_paste_params* p, const int32_t* origin, void* stream);
+
+/* ---------------------------------------------------------------- multi-subject matting ----------
+ * One clip, S subjects (an extension; otvm_amd/subjects.py, run_video_matte_subjects): every subject is followed by a tracking
+ * window of its own, the S windows share ONE size h x w and go through the network as one lock-step batch.  These are the tracking
+ * window's glue launches over S subjects at once -- the launches of a step do not grow with S -- and the one new pass, the resolve,
+ * which pastes the S windows into the frame and settles the pixels where they overlap.  Conventions as above: the caller's stream,
+ * no host synchronisation, nothing launched when an argument is refused (nonzero; otvm_last_error() starts with the function's
+ * name), sides 1 .. 16383, S = 1 .. OTVM_SUBJECTS_MAX.  Per-subject BUFFERS are fixed arrays of 8 pointers (entries s >= S are not
+ * looked at); per-subject ROWS of int32 words are `base + s * stride` (stride in words, any sign), so that one [S,T,10] log --
+ * words 0 .. 7 the boxes of a frame's output trimap in its window, words 8, 9 the window's origin -- is indexed as it lies.  An
+ * origin read from device memory is CLAMPED to [0, H - h] x [0, W - w] before any address is formed from it.  Checked by definition
+ * only, like the tracking window.  New symbols only (additive, as the entries above): the ABI number stays.                   */
+#define OTVM_SUBJECTS_MAX 8
+
+/* otvm_subjects_track: otvm_roi_track for S subjects in one launch of 2 S threads: thread (s, axis) applies that policy to
+ * box_base + s * box_stride (8 words), prev_base + s * prev_stride (2 words; prev_base NULL: every subject centres on its box,
+ * which is then in frame coordinates) and writes out_base + s * out_stride (2 words).  Bit-equal to S otvm_roi_track calls.   */
+typedef struct otvm_subjects_track_params {
+    int S;
+    const int32_t* box_base;   int box_stride;
+    const int32_t* prev_base;  int prev_stride;     /* prev_base NULL: a step with a source */
+    int32_t* out_base;         int out_stride;
+    int H, W, h, w, hold;
+} otvm_subjects_track_params;
+int otvm_subjects_track(const otvm_subjects_track_params* p, void* stream);
+
+/* otvm_subjects_crop: the frame uint8 [H,W,3] -> S windows [h,w,3] at the S origins (origin_base + s * origin_stride, 2 words),
+ * and / or S trimaps float [3,H,W] -> [3,h,w] at the same origins, in ONE launch.  Pure copies: for every s bit-equal to
+ * otvm_roi_crop_at.  A destination set is given for all s < S or for none; one of the two at least.                          */
+typedef struct otvm_subjects_crop_params {
+    int S, H, W, h, w;
+    const int32_t* origin_base;  int origin_stride;
+    const uint8_t* frame;                            /* [H,W,3], or NULL without frame_out */
+    uint8_t* frame_out[OTVM_SUBJECTS_MAX];           /* [h,w,3] each, or all NULL */
+    const float* trimap[OTVM_SUBJECTS_MAX];          /* [3,H,W] each, or NULL without trimap_out */
+    float* trimap_out[OTVM_SUBJECTS_MAX];            /* [3,h,w] each, or all NULL */
+} otvm_subjects_crop_params;
+int otvm_subjects_crop(const otvm_subjects_crop_params* p, void* stream);
+
+/* otvm_subjects_bbox: otvm_trimap_bbox of S float trimaps [3,H,W] (H x W here is the maps' own size) into the 8 words at
+ * out_base + s * out_stride: two launches whatever S is (the empty boxes, then the reduction with integer min / max atomics).
+ * For every s bit-equal to otvm_trimap_bbox.                                                                                  */
+typedef struct otvm_subjects_bbox_params {
+    int S, H, W;
+    const float* trimap[OTVM_SUBJECTS_MAX];
+    int32_t* out_base;  int out_stride;
+} otvm_subjects_bbox_params;
+int otvm_subjects_bbox(const otvm_subjects_bbox_params* p, void* stream);
+
+/* otvm_subjects_resolve: the S windows' results at H x W in ONE sweep.  Every output is optional (at least one), every element
+ * of a requested output is written; fp32, one IEEE operation per step, no atomics (two calls give equal bits).  Per pixel:
+ *   a_s      = the window's alpha where the pixel lies in subject s's window, 0.f elsewhere (everything outside a tracking
+ *              window is background, as otvm_roi_paste_at with outside == NULL);
+ *   sum      = ((a_0 + a_1) + a_2) + ... in subject order;
+ *   normalise != 0 and sum > 1.f: a_s = a_s / sum (correctly rounded; a NaN sum fails the comparison: nothing is rescaled);
+ *   alpha[s] = a_s; alpha_u8[s] = otvm_roi_paste's byte of it (a non-finite alpha gives 0);
+ *   trimap[s]= the window's trimap inside the window, (1, 0, 0) outside; never rescaled;
+ *   fgr[s]   = the window's F inside the window, (float)byte * (1.f / 255.f) of the frame's pixel outside, stored R, G, B;
+ *   union    = fminf(sum, 1.f) of the UNNORMALISED sum, union_u8 its byte;
+ *   owner    = the smallest s whose written a_s is largest and > 0.f, 255 when there is none.
+ * With normalise == 0 every per-subject plane is bit-equal to otvm_roi_paste_at of that subject.  The rule of `normalise` is an
+ * untuned PLACEHOLDER.  fgr needs win_fgr for every s < S and the frame.                                                       */
+typedef struct otvm_subjects_resolve_params {
+    int S, H, W, h, w;
+    const int32_t* origin_base;  int origin_stride;
+    const float* win_alpha[OTVM_SUBJECTS_MAX];       /* [h,w] each */
+    const float* win_trimap[OTVM_SUBJECTS_MAX];      /* [3,h,w] each */
+    const float* win_fgr[OTVM_SUBJECTS_MAX];         /* [3,h,w] R, G, B each, or NULL without fgr */
+    const uint8_t* frame;                            /* [H,W,3], or NULL without fgr */
+    int u8_rgb, normalise;
+    float* alpha;                                    /* [S,H,W] */
+    uint8_t* alpha_u8;                               /* [S,H,W] */
+    float* trimap;                                   /* [S,3,H,W] */
+    float* fgr;                                      /* [S,3,H,W] R, G, B */
+    float* union_alpha;                              /* [H,W] */
+    uint8_t* union_u8;                               /* [H,W] */
+    uint8_t* owner;                                  /* [H,W] */
+} otvm_subjects_resolve_params;
+int otvm_subjects_resolve(const otvm_subjects_resolve_params* p, void* stream);
 
 /* ---------------------------------------------------------------- range guard / clear -----------
  * f16x3 splits fp32 operands into fp16 halves: |x| >= 65504 loses accuracy, >= 131008 becomes inf.

@@ -34,6 +34,7 @@ SOURCES = [
     ("mask_trimap.hip", ["-ffp-contract=off"]),
     ("temporal.hip", ["-ffp-contract=off"]),
     ("roi.hip", ["-ffp-contract=off"]),
+    ("subjects.hip", ["-ffp-contract=off"]),
     ("memory_read.hip", []),
     ("memory_read_f16x3.hip", []),
     ("metrics.hip", []),

@@ -51,6 +51,15 @@ source's box plus the margin), an origin per frame that lives on the device and 
 for the neighbouring frame (otvm_roi_track; roi.track_origin is the policy), so the window lags ONE frame: a subject that moves more
 than max(1, margin // 2) pixels a frame, or outgrows the size, is cut, and roi_clipped lists those frames.  Nothing is read back
 inside the frame loop.  The same exclusions as --roi auto, and refused with --masks frame (auto tracks there).
+--subjects [--subjects-overlap keep|normalise] (demo layout): one matte per subject of a clip (subjects.run_video_matte_subjects).
+Every sub-directory of <seq>/subjects/ (beside trimap/) is one subject, in sorted order; its trimap is the PNG carrying the first
+frame's stem, decoded as trimap/ is.  With --roi track[,H,W] every subject is followed by a tracking window of its own, all of one
+size, and the windows run as one lock-step batch; without --roi the subjects run at full frames.  Per-subject alphas go to
+<out>/.../pred/<seq>/<subject>/, their union (min(sum, 1)) to <out>/.../pred/<seq>/, with --fgr the RGBA to
+<out>/fgr/<seq>/<subject>/.  normalise divides the alphas of a pixel by their sum where it exceeds 1 (an untuned PLACEHOLDER).
+Checked by definition only.  Refused without --demo, with --roi auto or a static window, --keyframes, --masks, --work-scale,
+--stabilise, --viz, --composite and --batch > 1.  The summary carries subjects and subjects_overlap; between clips whose window
+size or number of subjects differs the engine's frame plans are dropped.
 Frame IO runs through otvm_amd/io_pipeline.py: the demo flow decodes ahead in a thread pool and uploads on a copy
 stream, both flows download the 8-bit alphas asynchronously and PNG-encode them in a pool (the reference's loop blocks
 on .cpu() + cv2.imwrite per frame, eval.py:209-217).
@@ -184,6 +193,13 @@ def main(argv=None):
                          "follow the propagated trimap, one frame behind")
     ap.add_argument("--roi-margin", type=int, default=None, metavar="M",
                     help="--roi auto: pixels kept round the subject's box (default 32: a placeholder, not tuned on real footage)")
+    ap.add_argument("--subjects", action="store_true",
+                    help="demo layout: one matte per subject -- every sub-directory of <seq>/subjects/ holds one subject's first-frame "
+                         "trimap; the subjects' tracking windows run as one lock-step batch (--roi track[,H,W], or no --roi: "
+                         "full frames)")
+    ap.add_argument("--subjects-overlap", default=None, choices=["keep", "normalise"],
+                    help="--subjects: where windows overlap keep every subject's alpha (default) or divide the alphas of a pixel by "
+                         "their sum where it exceeds 1 (a placeholder rule, not tuned on real footage)")
     ap.add_argument("--max-frames", type=int, default=None, help="only the first N frames of every sequence")
     ap.add_argument("--weights", default=None)
     ap.add_argument("--synthetic-weights", action="store_true")
@@ -247,6 +263,21 @@ def main(argv=None):
         raise SystemExit("eval_cli: --masks frame mattes every frame from its own mask and propagates nothing: there is no trimap "
                          "for --keyframes to place or correct; use --masks key")
 
+    if args.subjects_overlap is not None and not args.subjects:
+        raise SystemExit("eval_cli: --subjects-overlap belongs to --subjects")
+    if args.subjects:
+        if not args.demo:
+            raise SystemExit("eval_cli: --subjects reads the demo layout's subjects/ folder (a first-frame trimap per subject); add --demo")
+        if roi is not None and not (roi == "track" or roi[0] == "track"):
+            raise SystemExit("eval_cli: --subjects follows every subject with a tracking window of its own, all of one size: --roi "
+                             "track[,H,W] or no --roi (full frames); --roi auto and a static window belong to single-subject clips")
+        for on, flag in ((args.keyframes, "--keyframes"), (args.masks, "--masks"), (args.work_scale is not None, "--work-scale"),
+                         (stabilise is not None, "--stabilise"), (args.viz, "--viz"), (args.composite is not None, "--composite"),
+                         (args.batch is not None and args.batch > 1, "--batch > 1")):
+            if on:
+                raise SystemExit("eval_cli: --subjects mattes the subjects of ONE clip in lock-step through run_video_matte_subjects, "
+                                 "which does not implement %s" % flag)
+
     if args.gpus is not None and args.gpus > 1 and "RANK" not in os.environ:
         import subprocess
         import sys
@@ -305,7 +336,7 @@ def main(argv=None):
         #  front -- so they keep batch 1 unless --batch is given explicitly)
         if world > 1 and any(k is not None for k in keys) and not (args.viz or args.sync_io or args.fgr or args.composite
                                                                    or args.keyframes or args.masks or stabilise is not None
-                                                                   or roi is not None):
+                                                                   or roi is not None or args.subjects):
             def padded(k):
                 lw, uw, lh, uh = pad_amounts(k[0], k[1], 32)
                 return (k[0] + lh + uh) * (k[1] + lw + uw)
@@ -344,7 +375,50 @@ def main(argv=None):
 
     roi_state = {"size": None}                        # --roi: the window size of the previous clip
 
+    def matte_subjects(seq):
+        """--subjects: every sub-directory of <seq>/subjects/ is one subject, in sorted order; its trimap is the PNG carrying the
+        first frame's stem, decoded as trimap/ is.  Per-subject alphas under <pred>/<seq>/<subject>/, the union at <pred>/<seq>/
+        (the usual place), with --fgr the RGBA under <out>/fgr/<seq>/<subject>/."""
+        from .subjects import run_video_matte_subjects
+        from .video import trimap_file_to_onehot
+        data = datasets.load_sequence(seq["item"], max_frames=args.max_frames, decode_frames=True, masks=True)   # (no trimap/ needed)
+        names, sdir = data["names"], os.path.join(seq["item"][1], seq["name"], "subjects")
+        who = sorted(d for d in os.listdir(sdir) if os.path.isdir(os.path.join(sdir, d))) if os.path.isdir(sdir) else []
+        if not who or not names:
+            raise SystemExit("eval_cli: --subjects found no subject for sequence %s (%s/<subject>/<first frame>.png)" % (seq["name"], sdir))
+        missing = [n for n in who if not os.path.isfile(os.path.join(sdir, n, names[0] + ".png"))]
+        if missing:
+            raise SystemExit("eval_cli: sequence %s: no first-frame trimap %s.png for subject(s) %s" % (seq["name"], names[0], ", ".join(missing)))
+        tris = [trimap_file_to_onehot(datasets.read_trimap_unchanged(os.path.join(sdir, n, names[0] + ".png"))) for n in who]
+        try:
+            res = run_video_matte_subjects(model, data["frames"], tris, roi=roi, roi_margin=roi_margin,
+                                           overlap=args.subjects_overlap or "keep", skip=args.skip, max_num=args.max_num,
+                                           frames_are_rgb=False, foreground=args.fgr, device=dev)
+        except ValueError as e:
+            raise SystemExit("eval_cli: sequence %s: %s" % (seq["name"], e))
+        outdir = os.path.join(root_out, "pred", seq["name"])
+        for s, n in enumerate([None] + who):
+            planes = res["union_u8"] if n is None else res["alpha_u8"][s - 1]
+            d = outdir if n is None else os.path.join(outdir, n)
+            os.makedirs(d, exist_ok=True)
+            for t, stem in enumerate(names):
+                Image.fromarray(planes[t].numpy()).save(os.path.join(d, stem + ".png"))
+                if args.fgr and n is not None:
+                    fd = os.path.join(args.out, "fgr", seq["name"], n)
+                    os.makedirs(fd, exist_ok=True)
+                    rgba = res["fgr_u8"][s - 1, t].numpy()                      # the frames are decoded B, G, R here
+                    Image.fromarray(rgba[..., [2, 1, 0, 3]].copy()).save(os.path.join(fd, stem + ".png"))
+        # every (window size, S) is a frame plan of its own and nothing else evicts them (as --roi)
+        key = [list(res["roi_size"]), len(who)]
+        if roi_state["size"] is not None and roi_state["size"] != key:
+            model.module.drop_plans()
+        roi_state["size"] = key
+        return dict(subjects=who, roi=[[list(w) for w in ws] for ws in res["roi"]], roi_size=list(res["roi_size"]),
+                    roi_clipped=res["roi_clipped"], bank_frames=res["bank_frames"])
+
     def matte(seq):
+        if args.subjects:
+            return matte_subjects(seq)
         demo = seq["item"][0] == "demo"
         keyed = demo and (args.keyframes or args.masks == "key")   # frames in schedule order: decoded up front, not prefetched
         data = datasets.load_sequence(seq["item"], max_frames=args.max_frames, decode_frames=not demo or args.sync_io or keyed,
@@ -503,6 +577,9 @@ def main(argv=None):
         summary["roi"], summary["roi_margin"] = (roi if isinstance(roi, str) else list(roi)), roi_margin
         summary["roi_size"] = {seqs[i]["name"]: o["roi_size"] for i, o in summary["outputs"].items() if o.get("roi_size")}
         summary["roi_clipped"] = {seqs[i]["name"]: o["roi_clipped"] for i, o in summary["outputs"].items() if "roi_clipped" in o}
+    if args.subjects:
+        summary["subjects"] = {seqs[i]["name"]: o["subjects"] for i, o in summary["outputs"].items() if "subjects" in o}
+        summary["subjects_overlap"] = args.subjects_overlap or "keep"
     if stabilise is not None:
         summary["stabilise"] = {k: stabilise.get(k, d) for k, d in (("strength", 0.5), ("tau_colour", 24.0), ("tau_alpha", 0.5),
                                                                       ("region", "unknown"))}

@@ -123,6 +123,30 @@ class RoiTrackParams(C.Structure):
     _fields_ = [("box", vp), ("prev", vp), ("out", vp), ("H", i32), ("W", i32), ("h", i32), ("w", i32), ("hold", i32)]
 
 
+SUBJECTS_MAX = 8        # include/otvm_hip.h OTVM_SUBJECTS_MAX
+
+
+class SubjectsTrackParams(C.Structure):
+    _fields_ = [("S", i32), ("box_base", vp), ("box_stride", i32), ("prev_base", vp), ("prev_stride", i32), ("out_base", vp),
+                ("out_stride", i32), ("H", i32), ("W", i32), ("h", i32), ("w", i32), ("hold", i32)]
+
+
+class SubjectsCropParams(C.Structure):
+    _fields_ = [("S", i32), ("H", i32), ("W", i32), ("h", i32), ("w", i32), ("origin_base", vp), ("origin_stride", i32),
+                ("frame", vp), ("frame_out", vp * SUBJECTS_MAX), ("trimap", vp * SUBJECTS_MAX), ("trimap_out", vp * SUBJECTS_MAX)]
+
+
+class SubjectsBboxParams(C.Structure):
+    _fields_ = [("S", i32), ("H", i32), ("W", i32), ("trimap", vp * SUBJECTS_MAX), ("out_base", vp), ("out_stride", i32)]
+
+
+class SubjectsResolveParams(C.Structure):
+    _fields_ = [("S", i32), ("H", i32), ("W", i32), ("h", i32), ("w", i32), ("origin_base", vp), ("origin_stride", i32),
+                ("win_alpha", vp * SUBJECTS_MAX), ("win_trimap", vp * SUBJECTS_MAX), ("win_fgr", vp * SUBJECTS_MAX),
+                ("frame", vp), ("u8_rgb", i32), ("normalise", i32), ("alpha", vp), ("alpha_u8", vp), ("trimap", vp), ("fgr", vp),
+                ("union_alpha", vp), ("union_u8", vp), ("owner", vp)]
+
+
 class PpmHeadParams(C.Structure):
     _fields_ = [("pooled", vp), ("C", i32), ("K_pad", i32), ("Cout", i32),
                 ("w", vp * 4), ("bias", vp * 4), ("gamma", vp * 4), ("beta", vp * 4), ("out", vp * 4),
@@ -206,6 +230,10 @@ _PROTOS = {
     "otvm_roi_track": (i32, [C.POINTER(RoiTrackParams), vp]),
     "otvm_roi_crop_at": (i32, [C.POINTER(RoiCropParams), vp, vp]),
     "otvm_roi_paste_at": (i32, [C.POINTER(RoiPasteParams), vp, vp]),
+    "otvm_subjects_track": (i32, [C.POINTER(SubjectsTrackParams), vp]),
+    "otvm_subjects_crop": (i32, [C.POINTER(SubjectsCropParams), vp]),
+    "otvm_subjects_bbox": (i32, [C.POINTER(SubjectsBboxParams), vp]),
+    "otvm_subjects_resolve": (i32, [C.POINTER(SubjectsResolveParams), vp]),
     "otvm_gn_stats_b": (i32, [vp, i64, i32, i32, vp, i32, i64, i32, vp]),
     "otvm_gn_table_b": (i32, [vp, i64, i32, vp, vp, vp, vp, i32, i32, i32, vp]),
     "otvm_gn_apply_b": (i32, [C.POINTER(GnApplyParams), vp]),
