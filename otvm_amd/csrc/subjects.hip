@@ -1,189 +1,48 @@
 // Multi-subject matting (include/otvm_hip.h: otvm_subjects_track, otvm_subjects_crop, otvm_subjects_bbox, otvm_subjects_resolve):
 // one clip, S subjects, each followed by a tracking window of its own; the S windows share one size and go through the network
-// as one lock-step batch.  The first three are roi.hip's tracking-window launches over S subjects at once -- the subject is the
-// grid's y (crop, bbox) or a thread pair (track) -- so that the launches of a step do not grow with S; for every s they give the
-// bits of roi.hip's single-subject forms, by test.  The resolve is the new pass: one sweep over H x W that pastes the S windows
-// and settles the pixels where they overlap.  Compiled with -ffp-contract=off: tests/subjects_ref.py restates the resolve
-// operation by operation, compared bit for bit.
-//
-// The access pattern is roi.hip's: a thread takes four consecutive pixels of one row of the FULL-SIZE, aligned side (the source
-// of the box, the destination of the crop, the outputs of the resolve); 16-byte, dword and 3-dword accesses when the width is a
-// multiple of four and the bases are aligned, pixel by pixel otherwise.  The window side is read element by element.
+// as one lock-step batch.  The first three are the tracking-window launches of roi.hip over S subjects at once -- the subject is
+// the grid's y (crop, bbox) or a thread pair (track) -- so that the launches of a step do not grow with S; the bodies are
+// window_ops.h's, the ones roi.hip's single-subject kernels call (and the tests still hold every s against those).  The resolve is
+// this file's own pass: one sweep over H x W that pastes the S windows and settles the pixels where they overlap.  Compiled with
+// -ffp-contract=off: tests/subjects_ref.py restates the resolve operation by operation, compared bit for bit.
 //
 // Per-subject buffers come as arrays of OTVM_SUBJECTS_MAX pointers in the params struct (the engine's batched outputs are separate
 // tensors); per-subject rows of int32 words as base + s * stride, so that one [S,T,10] log is indexed as it lies.  Whatever an
-// origin row holds is clamped to [0, H - h] x [0, W - w] before any address is formed from it (sub_origin_at, roi.hip's
-// roi_origin_at restated).
-#include "common.h"
+// origin row holds is clamped to [0, H - h] x [0, W - w] before any address is formed from it (win_origin_at).
+#include "window_ops.h"
 
 namespace {
 
-typedef float sub_f32x4 __attribute__((ext_vector_type(4)));
-constexpr int SUB_MAX_SIDE = 16383;
-constexpr int SUB_MAX_BLOCKS = 2048;
 constexpr int SMAX = OTVM_SUBJECTS_MAX;
 
-__device__ __forceinline__ bool sub_finite(float v) { return fabsf(v) < __builtin_inff(); }
-
-__device__ __forceinline__ int sub_origin_at(const int* __restrict__ origin, int axis, int full, int side) {
-    const int v = origin[axis], hi = full - side;
-    return v < 0 ? 0 : (v > hi ? hi : v);
-}
-
-__device__ __forceinline__ unsigned sub_byte(float a) {
-    const float v = fminf(fmaxf(truncf(a * 255.f), 0.f), 255.f);
-    return sub_finite(a) ? (unsigned)(int)v : 0u;
-}
-
-// thread 2 s decides y of subject s, thread 2 s + 1 its x: roi_track_kernel's policy on the subject's own rows
+// thread 2 s decides y of subject s, thread 2 s + 1 its x, on the subject's own rows
 __global__ __launch_bounds__(64) void subjects_track_kernel(const otvm_subjects_track_params p) {
     const int t = threadIdx.x;
     if (t >= 2 * p.S) return;
-    const int s = t >> 1, a = t & 1;
-    const int* box = p.box_base + (int64_t)s * p.box_stride;
-    const int* prev = p.prev_base ? p.prev_base + (int64_t)s * p.prev_stride : nullptr;
-    int* out = p.out_base + (int64_t)s * p.out_stride;
-    const int full = a ? p.W : p.H, side = a ? p.w : p.h, top = full - side;
-    const bool empty = box[6] < box[4] || box[7] < box[5];
-    const int64_t lo = box[4 + a], hi = box[6 + a];
-    int o = 0;
-    bool held = empty;                                     // an empty box keeps the neighbour's origin ((0, 0) without one)
-    if (prev) {
-        o = sub_origin_at(prev, a, full, side);
-        held = held || ((lo >= p.hold || o == 0) && (side - 1 - hi >= p.hold || o == top));
-    }
-    if (!held) {
-        const int64_t c = o + ((lo + hi + 1) >> 1) - (side >> 1);
-        o = (int)(c < 0 ? 0 : (c > top ? top : c));
-    }
-    out[a] = o;
+    const int s = t >> 1;
+    win_track_axis(p.box_base + (int64_t)s * p.box_stride, p.prev_base ? p.prev_base + (int64_t)s * p.prev_stride : nullptr,
+                   p.out_base + (int64_t)s * p.out_stride, t & 1, p.H, p.W, p.h, p.w, p.hold);
 }
 
-// blockIdx.y is the subject; a thread takes four consecutive pixels of one WINDOW row (roi_crop_kernel's body)
+// blockIdx.y is the subject
 template <bool VEC>
 __global__ __launch_bounds__(256) void subjects_crop_kernel(const otvm_subjects_crop_params p) {
     const int s = blockIdx.y;
     const int* origin = p.origin_base + (int64_t)s * p.origin_stride;
-    const int wy0 = sub_origin_at(origin, 0, p.H, p.h), wx0 = sub_origin_at(origin, 1, p.W, p.w);
-    uint8_t* __restrict__ frame_out = p.frame_out[s];
-    const float* __restrict__ trimap = p.trimap[s];
-    float* __restrict__ trimap_out = p.trimap_out[s];
-    const int n4 = (p.w + 3) >> 2;
-    const int64_t total = (int64_t)p.h * n4, P = (int64_t)p.H * p.W, M = (int64_t)p.h * p.w;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int y = (int)(t / n4), x0 = (int)(t - (int64_t)y * n4) * 4;
-        const int n = p.w - x0 < 4 ? p.w - x0 : 4;
-        const int64_t src = (int64_t)(y + wy0) * p.W + (x0 + wx0), dst = (int64_t)y * p.w + x0;
-        if (frame_out) {
-            unsigned by[12];
-#pragma unroll
-            for (int j = 0; j < 12; ++j) by[j] = j < 3 * n ? (unsigned)p.frame[src * 3 + j] : 0u;
-            if (VEC) {
-                unsigned* d = reinterpret_cast<unsigned*>(frame_out + dst * 3);
-#pragma unroll
-                for (int q = 0; q < 3; ++q) d[q] = by[4 * q] | (by[4 * q + 1] << 8) | (by[4 * q + 2] << 16) | (by[4 * q + 3] << 24);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 12; ++j)
-                    if (j < 3 * n) frame_out[dst * 3 + j] = (uint8_t)by[j];
-            }
-        }
-        if (trimap_out) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                float v[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = j < n ? trimap[k * P + src + j] : 0.f;
-                if (VEC) {
-                    *reinterpret_cast<sub_f32x4*>(trimap_out + k * M + dst) = sub_f32x4{v[0], v[1], v[2], v[3]};
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (j < n) trimap_out[k * M + dst + j] = v[j];
-                }
-            }
-        }
-    }
+    win_crop_rows<VEC>(p.frame, p.frame_out[s], p.trimap[s], p.trimap_out[s], nullptr, nullptr, p.H, p.W, p.h, p.w,
+                       win_origin_at(origin, 0, p.H, p.h), win_origin_at(origin, 1, p.W, p.w), WIN_FIRST, WIN_STEP);
 }
 
 __global__ __launch_bounds__(64) void subjects_bbox_init_kernel(const otvm_subjects_bbox_params p) {
     const int t = threadIdx.x, s = t >> 3, i = t & 7;
-    if (s < p.S) (p.out_base + (int64_t)s * p.out_stride)[i] = (i & 2) ? -1 : ((i & 1) ? p.W : p.H);
+    if (s < p.S) (p.out_base + (int64_t)s * p.out_stride)[i] = win_bbox_empty(p.H, p.W, i);
 }
 
-// blockIdx.y is the subject; roi_bbox_kernel's reduction of a float trimap (words 0, 1, 4, 5 minima, words 2, 3, 6, 7 maxima)
+// blockIdx.y is the subject; float trimaps only
 template <bool VEC>
 __global__ __launch_bounds__(256) void subjects_bbox_kernel(const otvm_subjects_bbox_params p) {
-    __shared__ int part_s[4][8];
-    const int s = blockIdx.y, H = p.H, W = p.W;
-    const float* __restrict__ tri = p.trimap[s];
-    int* __restrict__ out = p.out_base + (int64_t)s * p.out_stride;
-    const int n4 = (W + 3) >> 2;
-    const int64_t total = (int64_t)H * n4, P = (int64_t)H * W;
-    int b[8] = {H, W, -1, -1, H, W, -1, -1};
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int y = (int)(t / n4), x0 = (int)(t - (int64_t)y * n4) * 4;
-        const int n = W - x0 < 4 ? W - x0 : 4;
-        const int64_t o = (int64_t)y * W + x0;
-        unsigned unk = 0, nbg = 0;                         // one bit per pixel of the group
-        float c[3][4];
-        if (VEC) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const sub_f32x4 v = *reinterpret_cast<const sub_f32x4*>(tri + k * P + o);
-                c[k][0] = v.x; c[k][1] = v.y; c[k][2] = v.z; c[k][3] = v.w;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) c[k][j] = j < n ? tri[k * P + o + j] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const bool nb = j < n && (c[1][j] > c[0][j] || c[2][j] > c[0][j]);        // max(t1, t2) > t0
-            nbg |= (nb ? 1u : 0u) << j;
-            unk |= ((nb && c[1][j] >= c[2][j]) ? 1u : 0u) << j;
-        }
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            const unsigned m = g ? nbg : unk;
-            if (m) {
-                const int lo = x0 + __builtin_ctz(m), hi = x0 + 31 - __builtin_clz(m);
-                int* q = b + 4 * g;
-                q[0] = y < q[0] ? y : q[0];
-                q[1] = lo < q[1] ? lo : q[1];
-                q[2] = y > q[2] ? y : q[2];
-                q[3] = hi > q[3] ? hi : q[3];
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const int other = __shfl_xor(b[i], off, 64);
-            b[i] = (i & 2) ? (other > b[i] ? other : b[i]) : (other < b[i] ? other : b[i]);
-        }
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) part_s[wave][i] = b[i];
-    }
-    __syncthreads();
-    if (threadIdx.x < 8) {
-        const int i = threadIdx.x;
-        const bool is_max = (i & 2) != 0;
-        int v = part_s[0][i];
-        for (int wv = 1; wv < 4; ++wv) {
-            const int other = part_s[wv][i];
-            v = is_max ? (other > v ? other : v) : (other < v ? other : v);
-        }
-        // (a workgroup that found nothing holds the empty box: nothing to merge)
-        if (is_max) { if (v >= 0) atomicMax(out + i, v); }
-        else        { if (v < ((i & 1) ? W : H)) atomicMin(out + i, v); }
-    }
+    const int s = blockIdx.y;
+    win_bbox_reduce<VEC>(p.trimap[s], nullptr, p.H, p.W, p.out_base + (int64_t)s * p.out_stride, WIN_FIRST, WIN_STEP);
 }
 
 // a thread takes four consecutive pixels of one FRAME row and all S subjects of them.  The loops over the subjects are unrolled
@@ -198,8 +57,8 @@ __global__ __launch_bounds__(256) void subjects_resolve_kernel(const otvm_subjec
         oy[s] = 0; ox[s] = 0;
         if (s < S) {
             const int* origin = p.origin_base + (int64_t)s * p.origin_stride;
-            oy[s] = sub_origin_at(origin, 0, p.H, p.h);
-            ox[s] = sub_origin_at(origin, 1, p.W, p.w);
+            oy[s] = win_origin_at(origin, 0, p.H, p.h);
+            ox[s] = win_origin_at(origin, 1, p.W, p.w);
         }
     }
     const int n4 = (p.W + 3) >> 2;
@@ -246,10 +105,10 @@ __global__ __launch_bounds__(256) void subjects_resolve_kernel(const otvm_subjec
                 if (s < S && a[s][j] > best) { best = a[s][j]; own[j] = (unsigned)s; }
         }
         if (VEC) {
-            if (p.union_alpha) *reinterpret_cast<sub_f32x4*>(p.union_alpha + o) = sub_f32x4{un[0], un[1], un[2], un[3]};
+            if (p.union_alpha) *reinterpret_cast<f32x4*>(p.union_alpha + o) = f32x4{un[0], un[1], un[2], un[3]};
             if (p.union_u8) {
                 *reinterpret_cast<unsigned*>(p.union_u8 + o) =
-                    sub_byte(un[0]) | (sub_byte(un[1]) << 8) | (sub_byte(un[2]) << 16) | (sub_byte(un[3]) << 24);
+                    win_byte(un[0]) | (win_byte(un[1]) << 8) | (win_byte(un[2]) << 16) | (win_byte(un[3]) << 24);
             }
             if (p.owner) *reinterpret_cast<unsigned*>(p.owner + o) = own[0] | (own[1] << 8) | (own[2] << 16) | (own[3] << 24);
         } else {
@@ -257,7 +116,7 @@ __global__ __launch_bounds__(256) void subjects_resolve_kernel(const otvm_subjec
             for (int j = 0; j < 4; ++j) {
                 if (j < n) {
                     if (p.union_alpha) p.union_alpha[o + j] = un[j];
-                    if (p.union_u8) p.union_u8[o + j] = (uint8_t)sub_byte(un[j]);
+                    if (p.union_u8) p.union_u8[o + j] = (uint8_t)win_byte(un[j]);
                     if (p.owner) p.owner[o + j] = (uint8_t)own[j];
                 }
             }
@@ -268,17 +127,17 @@ __global__ __launch_bounds__(256) void subjects_resolve_kernel(const otvm_subjec
             if (s < S) {
                 const int64_t os = (int64_t)s * N + o;
                 if (VEC) {
-                    if (p.alpha) *reinterpret_cast<sub_f32x4*>(p.alpha + os) = sub_f32x4{a[s][0], a[s][1], a[s][2], a[s][3]};
+                    if (p.alpha) *reinterpret_cast<f32x4*>(p.alpha + os) = f32x4{a[s][0], a[s][1], a[s][2], a[s][3]};
                     if (p.alpha_u8) {
                         *reinterpret_cast<unsigned*>(p.alpha_u8 + os) =
-                            sub_byte(a[s][0]) | (sub_byte(a[s][1]) << 8) | (sub_byte(a[s][2]) << 16) | (sub_byte(a[s][3]) << 24);
+                            win_byte(a[s][0]) | (win_byte(a[s][1]) << 8) | (win_byte(a[s][2]) << 16) | (win_byte(a[s][3]) << 24);
                     }
                 } else {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         if (j < n) {
                             if (p.alpha) p.alpha[os + j] = a[s][j];
-                            if (p.alpha_u8) p.alpha_u8[os + j] = (uint8_t)sub_byte(a[s][j]);
+                            if (p.alpha_u8) p.alpha_u8[os + j] = (uint8_t)win_byte(a[s][j]);
                         }
                     }
                 }
@@ -338,8 +197,8 @@ __global__ __launch_bounds__(256) void subjects_resolve_kernel(const otvm_subjec
                 if (VEC) {
 #pragma unroll
                     for (int k = 0; k < 3; ++k) {
-                        if (p.trimap) *reinterpret_cast<sub_f32x4*>(p.trimap + os + k * N) = sub_f32x4{T[k][0], T[k][1], T[k][2], T[k][3]};
-                        if (p.fgr) *reinterpret_cast<sub_f32x4*>(p.fgr + os + k * N) = sub_f32x4{F[k][0], F[k][1], F[k][2], F[k][3]};
+                        if (p.trimap) *reinterpret_cast<f32x4*>(p.trimap + os + k * N) = f32x4{T[k][0], T[k][1], T[k][2], T[k][3]};
+                        if (p.fgr) *reinterpret_cast<f32x4*>(p.fgr + os + k * N) = f32x4{F[k][0], F[k][1], F[k][2], F[k][3]};
                     }
                 } else {
 #pragma unroll
@@ -358,18 +217,9 @@ __global__ __launch_bounds__(256) void subjects_resolve_kernel(const otvm_subjec
     }
 }
 
-bool sub_side_ok(int v) { return v >= 1 && v <= SUB_MAX_SIDE; }
-
-unsigned sub_blocks(int64_t rows, int width) {
-    const int64_t b = (rows * ((width + 3) / 4) + 255) / 256;
-    return (unsigned)(b > SUB_MAX_BLOCKS ? SUB_MAX_BLOCKS : b);
-}
-
 int sub_common_ok(const char* name, int S, int H, int W, int h, int w) {
     OTVM_REQUIRE(S >= 1 && S <= SMAX, "%s: 1 .. %d subjects, got %d", name, SMAX, S);
-    OTVM_REQUIRE(sub_side_ok(H) && sub_side_ok(W), "%s: the frame is 1 .. 16383 pixels a side, got %dx%d", name, H, W);
-    OTVM_REQUIRE(h >= 1 && w >= 1 && h <= H && w <= W, "%s: a %dx%d window does not fit the %dx%d frame", name, h, w, H, W);
-    return 0;
+    return win_window_ok(name, H, W, h, w);
 }
 
 }  // namespace
@@ -377,7 +227,7 @@ int sub_common_ok(const char* name, int S, int H, int W, int h, int w) {
 extern "C" int otvm_subjects_track(const otvm_subjects_track_params* p, void* stream) {
     OTVM_REQUIRE(p && p->box_base && p->out_base, "otvm_subjects_track: null pointer (params, box_base or out_base)");
     if (int rc = sub_common_ok("otvm_subjects_track", p->S, p->H, p->W, p->h, p->w)) return rc;
-    OTVM_REQUIRE(p->hold >= 1 && p->hold <= SUB_MAX_SIDE, "otvm_subjects_track: hold is 1 .. 16383 pixels, got %d", p->hold);
+    OTVM_REQUIRE(p->hold >= 1 && p->hold <= WIN_MAX_SIDE, "otvm_subjects_track: hold is 1 .. 16383 pixels, got %d", p->hold);
     OTVM_REQUIRE((((uintptr_t)p->box_base | (uintptr_t)p->prev_base | (uintptr_t)p->out_base) & 3) == 0,
                  "otvm_subjects_track: misaligned box_base, prev_base or out_base");
     hipLaunchKernelGGL(subjects_track_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *p);
@@ -409,7 +259,7 @@ extern "C" int otvm_subjects_crop(const otvm_subjects_crop_params* p, void* stre
     otvm_subjects_crop_params q = *p;
     for (int s = p->S; s < SMAX; ++s) { q.frame_out[s] = nullptr; q.trimap[s] = nullptr; q.trimap_out[s] = nullptr; }
     const bool vec = p->w % 4 == 0 && (out16_bits & 15) == 0 && (u8_bits & 3) == 0;
-    const dim3 grid(sub_blocks(p->h, p->w), (unsigned)p->S);
+    const dim3 grid(win_blocks(p->h, p->w), (unsigned)p->S);
     hipStream_t st = (hipStream_t)stream;
     if (vec) hipLaunchKernelGGL(subjects_crop_kernel<true>, grid, dim3(256), 0, st, q);
     else hipLaunchKernelGGL(subjects_crop_kernel<false>, grid, dim3(256), 0, st, q);
@@ -421,7 +271,7 @@ extern "C" int otvm_subjects_bbox(const otvm_subjects_bbox_params* p, void* stre
     const char* name = "otvm_subjects_bbox";
     OTVM_REQUIRE(p && p->out_base, "%s: null pointer (params or out_base)", name);
     OTVM_REQUIRE(p->S >= 1 && p->S <= SMAX, "%s: 1 .. %d subjects, got %d", name, SMAX, p->S);
-    OTVM_REQUIRE(sub_side_ok(p->H) && sub_side_ok(p->W), "%s: the map is 1 .. 16383 pixels a side, got %dx%d", name, p->H, p->W);
+    if (int rc = win_sides_ok(name, "map", p->H, p->W)) return rc;
     uintptr_t bits = (uintptr_t)p->out_base;
     for (int s = 0; s < p->S; ++s) {
         OTVM_REQUIRE(p->trimap[s], "%s: null trimap of subject %d", name, s);
@@ -433,7 +283,7 @@ extern "C" int otvm_subjects_bbox(const otvm_subjects_bbox_params* p, void* stre
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(subjects_bbox_init_kernel, dim3(1), dim3(64), 0, st, *p);
     const bool vec = p->W % 4 == 0 && (tri_bits & 15) == 0;
-    const dim3 grid(sub_blocks(p->H, p->W), (unsigned)p->S);
+    const dim3 grid(win_blocks(p->H, p->W), (unsigned)p->S);
     if (vec) hipLaunchKernelGGL(subjects_bbox_kernel<true>, grid, dim3(256), 0, st, *p);
     else hipLaunchKernelGGL(subjects_bbox_kernel<false>, grid, dim3(256), 0, st, *p);
     OTVM_CHECK_LAUNCH(name);
@@ -459,7 +309,7 @@ extern "C" int otvm_subjects_resolve(const otvm_subjects_resolve_params* p, void
     OTVM_REQUIRE((f32_bits & 3) == 0, "%s: misaligned fp32 plane", name);
     const bool vec = p->W % 4 == 0 && (out16_bits & 15) == 0 &&
                      (((uintptr_t)p->alpha_u8 | (uintptr_t)p->union_u8 | (uintptr_t)p->owner | (uintptr_t)p->frame) & 3) == 0;
-    const dim3 grid(sub_blocks(p->H, p->W));
+    const dim3 grid(win_blocks(p->H, p->W));
     hipStream_t st = (hipStream_t)stream;
     if (vec) hipLaunchKernelGGL(subjects_resolve_kernel<true>, grid, dim3(256), 0, st, *p);
     else hipLaunchKernelGGL(subjects_resolve_kernel<false>, grid, dim3(256), 0, st, *p);

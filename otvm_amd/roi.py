@@ -10,6 +10,7 @@ The tracking window (run_video_matte(roi="track")): otvm_roi_track, otvm_roi_cro
 on the device, a row of an int32 log per frame; track_origin is the same policy on the host, and rows_of the one read-back."""
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import lib as L
@@ -118,6 +119,58 @@ def check_window(window, H, W, who="otvm_amd.roi"):
     return y0, x0, h, w
 
 
+# ---- roi="track" as run_video_matte and run_video_matte_subjects both take it (``who``: the route, which keeps its messages)
+def track_spec(spec, who):
+    """'track' -> ("track",), ('track', h, w) -> ("track", h, w) with ints; None for every other form (the caller's own)."""
+    if isinstance(spec, str):
+        return ("track",) if spec == "track" else None
+    if not (isinstance(spec, (tuple, list)) and len(spec) == 3 and spec[0] == "track"):
+        return None
+    if not all(not isinstance(v, bool) and isinstance(v, (int, np.integer)) for v in spec[1:]) or spec[1] < 1 or spec[2] < 1:
+        raise ValueError("%s: roi = ('track', h, w) needs integers h, w >= 1, got %r" % (who, spec))
+    return ("track", int(spec[1]), int(spec[2]))
+
+
+def check_margin(margin, who):
+    if isinstance(margin, bool) or not isinstance(margin, (int, np.integer)) or margin < 0:
+        raise ValueError("%s: roi_margin is a number of pixels >= 0 (an integer), got %r" % (who, margin))
+    return int(margin)
+
+
+def check_hold(hold, who="otvm_amd.roi"):
+    if isinstance(hold, bool) or int(hold) != hold or hold < 1:
+        raise ValueError("%s: hold is a number of pixels >= 1 (an integer), got %r" % (who, hold))
+    return int(hold)
+
+
+def track_size(boxes, spec, margin, H, W, who, what):
+    """(h, w) of the ONE size a clip's tracking windows share, from ``boxes`` = {label: non-background box of a source}: window_size
+    over all of them for ("track",); ("track", h, w) as given, refused when a box does not fit (``what`` % label names its source)."""
+    if len(spec) != 3:
+        return window_size(list(boxes.values()), H, W, margin)
+    h, w = check_size(spec[1:], H, W, who + ": roi")
+    for label, box in sorted(boxes.items()):
+        if not is_empty(box) and (box[2] - box[0] + 1 > h or box[3] - box[1] + 1 > w):
+            raise ValueError("%s: the %dx%d window of roi = %r does not hold %s (its classes other than background: rows %d ... %d, "
+                             "columns %d ... %d)" % (who, h, w, spec, what % label, box[0], box[2], box[1], box[3]))
+    return h, w
+
+
+def new_log(rows_shape, h, w, dev):
+    """The int32 [*rows_shape, 10] log of a tracked clip.  Per row: words 0 .. 7 the boxes of the frame's output trimap (in the frame's
+    window), words 8, 9 the window's origin -- ONE buffer, read back with one copy after the last frame.  Rows start as the empty
+    box at (0, 0)."""
+    return torch.tensor([h, w, -1, -1, h, w, -1, -1, 0, 0], dtype=torch.int32, device=dev).repeat(*rows_shape, 1)
+
+
+def clipped(rows, size, H, W, seen):
+    """Read-back rows (eight box words in window coordinates, then the origin) -> (roi: [(y0, x0, h, w) per row], roi_clipped: the
+    i of ``seen`` whose non-background box reaches a side of its window that is not a side of the frame)."""
+    wins = [(r[8], r[9]) + tuple(size) for r in rows]
+    in_frame = lambda r: (r[4] + r[8], r[5] + r[9], r[6] + r[8], r[7] + r[9])                 # (an empty box stays empty)
+    return wins, [i for i in sorted(seen) if touched_sides(wins[i], in_frame(rows[i]), H, W)]  # box words of other rows: not looked at
+
+
 # ------------------------------------------------------------------ the kernels round device tensors
 def _source(src, who):
     """A class map as the kernels take it: ('trimap', float [3,H,W]) or ('labels', uint8 [H,W]), contiguous, on the GPU."""
@@ -149,7 +202,8 @@ def trimap_bbox(src, out=None):
 
 def rows_of(buf):
     """A device int32 [n,k] buffer as n host tuples: THE read-back of the tracking window -- the source boxes before the first
-    frame, the origin log and the output boxes after the last -- and nothing in between."""
+    frame, the origin log and the output boxes after the last -- and nothing in between.  (The static window reads its output
+    boxes back through it too, once, after the last frame.)"""
     return [tuple(r) for r in buf.cpu().view(buf.shape[0], -1).tolist()]
 
 
@@ -184,11 +238,9 @@ def track(box, prev, out, size, H, W, hold):
     if prev is not None:
         _origin_row(prev, dev, "track's prev")
     h, w = check_size(size, H, W)
-    if isinstance(hold, bool) or int(hold) != hold or hold < 1:
-        raise ValueError("otvm_amd.roi: hold is a number of pixels >= 1 (an integer), got %r" % (hold,))
     p = L.RoiTrackParams()
     p.box, p.prev, p.out = box.data_ptr(), None if prev is None else prev.data_ptr(), out.data_ptr()
-    p.H, p.W, p.h, p.w, p.hold = H, W, h, w, int(hold)
+    p.H, p.W, p.h, p.w, p.hold = H, W, h, w, check_hold(hold)
     L.check(L.load().otvm_roi_track(C.byref(p), _stream(dev)), "roi_track")
     return out
 

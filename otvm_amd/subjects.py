@@ -37,33 +37,18 @@ def rows_of(buf):
 
 # ------------------------------------------------------------------ the shared window (host only)
 def shared_size(boxes, spec, margin, H, W):
-    """(h, w) of the ONE window size all subjects share.  ``boxes``: the non-background box (y0, x0, y1, x1) of every subject's
-    first-frame trimap; ``spec``: ("track",) -- roi.window_size over all the boxes: the largest extent plus twice the margin,
-    rounded up to 32 -- or ("track", h, w): as given, refused when a subject's box does not fit."""
-    if len(spec) == 3:
-        h, w = _roi.check_size(spec[1:], H, W, WHO + ": roi")
-        for s, box in enumerate(boxes):
-            if not _roi.is_empty(box) and (box[2] - box[0] + 1 > h or box[3] - box[1] + 1 > w):
-                raise ValueError("%s: the %dx%d window of roi = %r does not hold the trimap of subject %d (its classes other than "
-                                 "background: rows %d ... %d, columns %d ... %d)" % (WHO, h, w, spec, s, box[0], box[2], box[1], box[3]))
-        return h, w
-    return _roi.window_size(list(boxes), H, W, margin)
+    """(h, w) of the ONE window size all subjects share: roi.track_size over the non-background boxes of their first-frame trimaps"""
+    return _roi.track_size(dict(enumerate(boxes)), spec, margin, H, W, WHO, "the trimap of subject %d")
 
 
 def check_roi(spec, margin):
     """-> (None | ("track",) | ("track", h, w), margin): the forms run_video_matte_subjects takes, refused host-side otherwise."""
-    if isinstance(margin, bool) or not isinstance(margin, (int, np.integer)) or margin < 0:
-        raise ValueError("%s: roi_margin is a number of pixels >= 0 (an integer), got %r" % (WHO, margin))
-    if spec is None:
-        return None, int(margin)
-    if isinstance(spec, str) and spec == "track":
-        return ("track",), int(margin)
-    if isinstance(spec, (tuple, list)) and len(spec) == 3 and spec[0] == "track":
-        if not all(not isinstance(v, bool) and isinstance(v, (int, np.integer)) for v in spec[1:]) or spec[1] < 1 or spec[2] < 1:
-            raise ValueError("%s: roi = ('track', h, w) needs integers h, w >= 1, got %r" % (WHO, spec))
-        return ("track", int(spec[1]), int(spec[2])), int(margin)
-    raise ValueError("%s: roi is None, 'track' or ('track', h, w): every subject is followed by a window of its own, all of one "
-                     "size ('auto' and a static window (y0, x0, h, w) belong to run_video_matte), got %r" % (WHO, spec))
+    margin = _roi.check_margin(margin, WHO)
+    track = _roi.track_spec(spec, WHO)
+    if spec is not None and track is None:
+        raise ValueError("%s: roi is None, 'track' or ('track', h, w): every subject is followed by a window of its own, all of one "
+                         "size ('auto' and a static window (y0, x0, h, w) belong to run_video_matte), got %r" % (WHO, spec))
+    return track, margin
 
 
 # ------------------------------------------------------------------ the kernels round device tensors
@@ -102,9 +87,7 @@ def track(box, prev, out, size, H, W, hold):
     if prev is not None:
         p.prev_base, p.prev_stride = _rows(prev, S, 2, dev, "track's prev")
     h, w = _roi.check_size(size, H, W, "otvm_amd.subjects")
-    if isinstance(hold, bool) or int(hold) != hold or hold < 1:
-        raise ValueError("otvm_amd.subjects: hold is a number of pixels >= 1 (an integer), got %r" % (hold,))
-    p.H, p.W, p.h, p.w, p.hold = H, W, h, w, int(hold)
+    p.H, p.W, p.h, p.w, p.hold = H, W, h, w, _roi.check_hold(hold, "otvm_amd.subjects")
     L.check(L.load().otvm_subjects_track(C.byref(p), _stream(dev)), "subjects_track")
     return out
 
@@ -284,9 +267,7 @@ def run_video_matte_subjects(model, frames, subjects, roi="track", roi_margin=32
         source_rows = bbox(tri_full, torch.empty((S, 8), dtype=torch.int32, device=dev))
         h, w = shared_size([tuple(r[4:]) for r in rows_of(source_rows)], spec, margin, H, W)
         hold = _roi.hold_of(margin)
-        # per subject and frame: words 0 .. 7 the boxes of the output trimap (in the frame's window), words 8, 9 the window's
-        # origin -- ONE buffer, read back with one copy after the last frame.  Rows start as the empty box at (0, 0).
-        log = torch.tensor([h, w, -1, -1, h, w, -1, -1, 0, 0], dtype=torch.int32, device=dev).repeat(S, T, 1)
+        log = _roi.new_log((S, T), h, w, dev)                # a row per subject and frame
         tri_dev = None
     else:
         h, w = H, W
@@ -343,14 +324,5 @@ def _windows(log, S, T, H, W, h, w):
     """roi, roi_size and roi_clipped per subject (ONE read-back of the log, after the last frame; none without windows)"""
     if log is None:
         return dict(roi=[[(0, 0, H, W)] * T for _ in range(S)], roi_size=(H, W), roi_clipped=[[] for _ in range(S)])
-    rows = rows_of(log)
-    wins = [[(r[8], r[9], h, w) for r in rows[s]] for s in range(S)]
-    clipped = []
-    for s in range(S):
-        cl = []
-        for t, r in enumerate(rows[s]):
-            y0, x0, b = r[8], r[9], r[4:8]
-            if not _roi.is_empty(b) and _roi.touched_sides(wins[s][t], (b[0] + y0, b[1] + x0, b[2] + y0, b[3] + x0), H, W):
-                cl.append(t)
-        clipped.append(cl)
-    return dict(roi=wins, roi_size=(h, w), roi_clipped=clipped)
+    per_subject = [_roi.clipped(rows, (h, w), H, W, range(T)) for rows in rows_of(log)]
+    return dict(roi=[wins for wins, _ in per_subject], roi_size=(h, w), roi_clipped=[cut for _, cut in per_subject])

@@ -435,12 +435,9 @@ class _RegionOfInterest:
     @staticmethod
     def refuse(spec, margin, frames, alphas, backgrounds, work_scale, masks=None):
         """-> (the window as four ints, "auto", or ("track",) / ("track", h, w); the margin)"""
-        track = spec == "track" if isinstance(spec, str) else (isinstance(spec, (tuple, list)) and len(spec) == 3 and spec[0] == "track")
-        if track:
-            if not isinstance(spec, str):
-                if not all(not isinstance(v, bool) and isinstance(v, (int, np.integer)) for v in spec[1:]) or spec[1] < 1 or spec[2] < 1:
-                    raise ValueError("run_video_matte: roi = ('track', h, w) needs integers h, w >= 1, got %r" % (spec,))
-            spec = ("track",) + (() if isinstance(spec, str) else (int(spec[1]), int(spec[2])))
+        track = _roi.track_spec(spec, "run_video_matte")
+        if track is not None:
+            spec = track
             if masks is not None:
                 raise ValueError("run_video_matte: roi='track' follows a PROPAGATED trimap; `masks` mattes every frame from its own "
                                  "mask, and roi='auto' already tracks there")
@@ -457,8 +454,7 @@ class _RegionOfInterest:
             spec = tuple(int(v) for v in spec)
             if spec[0] < 0 or spec[1] < 0 or spec[2] < 1 or spec[3] < 1:
                 raise ValueError("run_video_matte: the window roi = (y0, x0, h, w) needs y0, x0 >= 0 and h, w >= 1, got %r" % (spec,))
-        if isinstance(margin, bool) or not isinstance(margin, (int, np.integer)) or margin < 0:
-            raise ValueError("run_video_matte: roi_margin is a number of pixels >= 0 (an integer), got %r" % (margin,))
+        margin = _roi.check_margin(margin, "run_video_matte")
         if alphas is not None:
             raise ValueError("run_video_matte: roi belongs to the trimap flow; the alphas flow (VideoMatting108: trimaps from "
                              "ground-truth alpha) has no region-of-interest route")
@@ -476,7 +472,7 @@ class _RegionOfInterest:
                 _roi.check_size(spec[1:], f0.shape[0], f0.shape[1], "run_video_matte: roi")
             elif not track and not isinstance(spec, str):
                 _roi.check_window(spec, f0.shape[0], f0.shape[1], "run_video_matte: roi")
-        return spec, int(margin)
+        return spec, margin
 
     def place_tracking(self, unknown, H, W):
         self.HW, self.tracking = (H, W), True
@@ -514,20 +510,9 @@ class _RegionOfInterest:
         """sources: {frame: the trimap / label map at H x W on the device}; source_rows: {frame: its int32 [8] box row on the
         device}; nonbg: {frame: its non-background box on the host} -- which decides the SIZE, and only that"""
         self.HW, self.sources, self.source_rows = (H, W), sources, source_rows
-        if len(self.spec) == 3:
-            h, w = _roi.check_size(self.spec[1:], H, W, "run_video_matte: roi")
-            for t, box in sorted(nonbg.items()):
-                if not _roi.is_empty(box) and (box[2] - box[0] + 1 > h or box[3] - box[1] + 1 > w):
-                    raise ValueError("run_video_matte: the %dx%d window of roi = %r does not hold the trimap / label map of frame %d "
-                                     "(its classes other than background: rows %d ... %d, columns %d ... %d)"
-                                     % (h, w, self.spec, t, box[0], box[2], box[1], box[3]))
-        else:
-            h, w = _roi.window_size(list(nonbg.values()), H, W, self.margin)
+        h, w = _roi.track_size(nonbg, self.spec, self.margin, H, W, "run_video_matte", "the trimap / label map of frame %d")
         self.track_size, self.hold = (h, w), _roi.hold_of(self.margin)
-        dev = next(iter(source_rows.values())).device
-        # per frame: words 0 .. 7 the boxes of the output trimap (in the frame's window), words 8, 9 the window's origin -- ONE
-        # buffer, so that result() reads the clip back with one copy.  Rows start as the empty box at (0, 0).
-        self.log = torch.tensor([h, w, -1, -1, h, w, -1, -1, 0, 0], dtype=torch.int32, device=dev).repeat(T, 1)
+        self.log = _roi.new_log((T,), h, w, next(iter(source_rows.values())).device)
 
     def window(self, i):
         return self.windows[i]
@@ -620,26 +605,16 @@ class _RegionOfInterest:
 
     def result(self):
         """roi, roi_size and roi_clipped (ONE read-back of the boxes, after the last frame)"""
-        clipped = []
         if self.follows:
             if self.log is None:
                 return dict(roi=[], roi_size=None, roi_clipped=[])
-            (H, W), (h, w) = self.HW, self.track_size
-            rows = _roi.rows_of(self.log)
-            self.windows = [(r[8], r[9], h, w) for r in rows]
-            for i in sorted(self.seen):
-                y0, x0, b = rows[i][8], rows[i][9], rows[i][4:8]
-                if not _roi.is_empty(b) and _roi.touched_sides(self.windows[i], (b[0] + y0, b[1] + x0, b[2] + y0, b[3] + x0), H, W):
-                    clipped.append(i)
+            self.windows, clipped = _roi.clipped(_roi.rows_of(self.log), self.track_size, *self.HW, self.seen)
             return dict(roi=list(self.windows), roi_size=self.size, roi_clipped=clipped)
+        clipped = []
         if self.rows is not None:
-            H, W = self.HW
-            boxes = _roi.boxes_of(self.rows)[1]
-            for i in sorted(self.seen):
-                y0, x0 = self.windows[i][:2]
-                b = boxes[i]
-                if not _roi.is_empty(b) and _roi.touched_sides(self.windows[i], (b[0] + y0, b[1] + x0, b[2] + y0, b[3] + x0), H, W):
-                    clipped.append(i)
+            assert all(win[2:] == self.size for win in self.windows)                 # place_static: ONE window for the clip
+            rows = [boxes + win[:2] for boxes, win in zip(_roi.rows_of(self.rows), self.windows)]       # (the fixed origins)
+            clipped = _roi.clipped(rows, self.size, *self.HW, self.seen)[1]
         return dict(roi=list(self.windows or []), roi_size=self.size, roi_clipped=clipped)
 
 

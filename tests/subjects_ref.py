@@ -3,13 +3,14 @@ compared bit for bit).  The integer track policy is not restated here: it is otv
 import numpy as np
 
 from tests.roi_ref import quant_u8
+from tests.roi_track_ref import clamp_origin as _clamp_origin
 
 F32 = np.float32
 
 
 def clamp_origin(origin, size, H, W):
-    """What the kernel makes of an origin row: clamped to [0, H - h] x [0, W - w]."""
-    return (min(max(int(origin[0]), 0), H - size[0]), min(max(int(origin[1]), 0), W - size[1]))
+    """What the kernels make of an origin row: roi_track_ref's clamp to [0, H - h] x [0, W - w], the size as one argument."""
+    return _clamp_origin(origin, size[0], size[1], H, W)
 
 
 def resolve(origins, size, H, W, alphas, trimaps, fgrs=None, frame=None, u8_rgb=False, normalise=False):

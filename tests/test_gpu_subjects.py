@@ -157,10 +157,11 @@ def test_crop_equals_s_single_subject_calls(lib, H, W, h, w, S, off):
         for s in range(S):
             rc1, f1, t1, _ = _crop_at_raw(lib, log[s, 1, 8:], (h, w), H, W, frame=fr, trimap=None if tr is None else tr[s])
             assert rc1 == 0
+            y0, x0 = SR.clamp_origin(log[s, 1, 8:].tolist(), (h, w), H, W)            # ... and the definition, for every subject
             if fr is not None:
-                assert torch.equal(fo[s], f1), (s, off)
+                assert torch.equal(fo[s], f1) and torch.equal(fo[s], frame[y0:y0 + h, x0:x0 + w]), (s, off)
             if tr is not None:
-                assert np.array_equal(bits(to[s]), bits(t1)), (s, off)
+                assert np.array_equal(bits(to[s]), bits(t1)) and torch.equal(to[s], tris[s][:, y0:y0 + h, x0:x0 + w]), (s, off)
     # ... and the definition: the window at the clamped origin
     y0, x0 = SR.clamp_origin(log[S - 1, 1, 8:].tolist(), (h, w), H, W)
     assert torch.equal(to[S - 1], tris[S - 1][:, y0:y0 + h, x0:x0 + w])
@@ -328,13 +329,17 @@ def test_resolve_equals_the_restatement(lib, H, W, h, w, normalise):
         a_np, t_np, f_np = _overlap_values(S, size[0], size[1], 17 + len(name))
         log = _log(origins)
         alphas, tris, fgrs = ([dev(x) for x in xs] for xs in (a_np, t_np, f_np))
-        for rgb, off in ((0, 0), (1, 1)):
-            ref = SR.resolve(origins, size, H, W, a_np, t_np, f_np, frame_np, bool(rgb), bool(normalise))
-            rc, got = _resolve_raw(lib, log[:, 1, 8:], H, W, size[0], size[1], alphas, tris, fgrs, frame, rgb, normalise, ALL, off)
-            rc2, again = _resolve_raw(lib, log[:, 1, 8:], H, W, size[0], size[1], alphas, tris, fgrs, frame, rgb, normalise, ALL, off)
+        # (the last two: R, G, B bytes through the 16-byte form, and no F at all -- the paste shares these bodies, so "equals S
+        # pastes" above does not hold them against anything)
+        for rgb, off, with_fgr in ((0, 0, True), (1, 1, True), (1, 0, True), (0, 0, False)):
+            want = ALL if with_fgr else tuple(k for k in ALL if k != "fgr")
+            args = (fgrs, frame) if with_fgr else (None, None)
+            ref = SR.resolve(origins, size, H, W, a_np, t_np, f_np if with_fgr else None, frame_np, bool(rgb), bool(normalise))
+            rc, got = _resolve_raw(lib, log[:, 1, 8:], H, W, size[0], size[1], alphas, tris, *args, rgb, normalise, want, off)
+            rc2, again = _resolve_raw(lib, log[:, 1, 8:], H, W, size[0], size[1], alphas, tris, *args, rgb, normalise, want, off)
             assert rc == 0 and rc2 == 0, lib.otvm_last_error()
-            for k in ALL:
-                assert np.array_equal(bits(got[k]), bits(ref[k])), (name, k, rgb, off)
+            for k in want:
+                assert np.array_equal(bits(got[k]), bits(ref[k])), (name, k, rgb, off, with_fgr)
                 assert np.array_equal(bits(got[k]), bits(again[k])), (name, k)
         # what the cases are there for
         total = sum(ref["alpha"][s] for s in range(S))
