@@ -233,17 +233,67 @@ class _EventClock:
         return [a.elapsed_time(b) for a, b in pairs]
 
 
+class Step:
+    """One entry of a launch list: the library call ``fn(*args, stream)``.  ``conv``, set where the step is made, marks a convolution
+    (counted into engine.conv_calls, timed by the instrumented pass, scanned at check level 3): it carries its algorithmic ``flops``
+    / ``abytes`` and the views it reads and writes (``src`` / ``dst``).  A step whose arguments need the GroupNorm statistics arena is
+    made with ``args`` None and ``late`` = callable(arena base, doubles per image) -> args (FramePlan.late_step, _bind_stats)."""
+    __slots__ = ("fn", "args", "label", "conv", "flops", "abytes", "src", "dst", "late")
+
+    def __init__(self, fn, args, label, conv=False, flops=0, abytes=0, src=None, dst=None, late=None):
+        self.fn, self.args, self.label, self.conv = fn, args, label, conv
+        self.flops, self.abytes, self.src, self.dst, self.late = flops, abytes, src, dst, late
+
+
+def _issue(steps, stream, eng=None, prof=None, scan=False, guard_in=False):
+    """THE loop that launches steps, on the raw stream handle ``stream``; a step whose late arguments were never bound is refused.
+    With nothing else given: the frame loop's direct launch (and what a graph capture records), L.check sees errors only.  With
+    ``eng`` every return code goes through L.check, and every convolution is either, with ``prof`` (a list), put between two HIP events
+    and appended as (label, flops, e0, e1, abytes), or, with ``scan`` (check level 3), followed by a scan of its output -- and with
+    ``guard_in`` preceded by one of its input."""
+    watch_convs = prof is not None or scan
+    for st in steps:
+        args = st.args
+        if args is None:
+            raise RuntimeError("otvm_amd: step %r in a launch list before its late arguments were bound" % (st.label,))
+        watch = watch_convs and st.conv
+        if watch:
+            if prof is not None:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+            elif guard_in:
+                eng.guard(st.src, "input of " + st.label, stream)
+        rc = st.fn(*args, stream)
+        if rc != 0 or eng is not None:
+            L.check(rc, st.label)
+        if watch:
+            if prof is not None:
+                e1.record()
+                prof.append((st.label, st.flops, e0, e1, st.abytes))
+            else:
+                eng.scan_now(st.dst, "output of " + st.label, stream)
+
+
+def _splice(S, old, new):
+    """Replace the step ``old`` of the launch list S -- found by identity -- by the steps ``new`` (none, one or several)."""
+    for i, st in enumerate(S):
+        if st is old:
+            S[i:i + 1] = new
+            return
+    raise ValueError("otvm_amd: step %r is not in this launch list" % (old.label,))
+
+
 def _time_candidates(eng, clock, steps_of, order, reps, warm=(), lead=0):
-    """THE plan-time timing protocol.  ``steps_of(c)`` returns the launch steps ``(fn, args, label, ...)`` of ONE repetition of
+    """THE plan-time timing protocol.  ``steps_of(c)`` returns the launch steps (Step) of ONE repetition of
     candidate ``c`` (and may set a parameter block to ``c`` first).  One repetition of every candidate in ``warm`` is thrown away;
     then every entry of ``order`` (candidates may repeat) is one measurement: ``lead`` untimed repetitions, ``reps`` timed ones
     between two marks of ``clock``.  Returns {candidate: ms per repetition, the minimum over its measurements}.  Every return code
-    is checked; the launches labelled "conv " are counted into ``eng.conv_calls`` (as FramePlan.run counts them)."""
+    is checked; the convolutions launched are counted into ``eng.conv_calls`` (as FramePlan.run counts them)."""
     def issue(c, n):
         for _ in range(n):
-            for st in steps_of(c):
-                L.check(st[0](*st[1], clock.stream), st[2])
-                eng.conv_calls += int(st[2].startswith("conv "))
+            steps = steps_of(c)
+            _issue(steps, clock.stream, eng)
+            eng.conv_calls += sum(st.conv for st in steps)
     for c in warm:
         issue(c, 1)
     marks = []
@@ -490,7 +540,7 @@ class HipEngine:
         self.pending = None          # deferred memorize of the previous frame
         self.ev_dec = None           # fires when the last STM decoder has read the query encoder's buffers
         self.frame_counter = 0
-        self.conv_calls = 0          # convolution launches issued by this engine (plan steps labelled "conv ", tuner launches included)
+        self.conv_calls = 0          # convolution launches issued by this engine (plan steps marked conv, tuner launches included)
         self.last_T_read = 0
         self.parity = 0
         self.side = None
@@ -1274,10 +1324,12 @@ class FramePlan:
         self.graphs, self._graph_warm = {}, {}
         self._n_conv = {}
         self._retired_graphs = []
-        self._stm128 = []                                     # launch lists holding an unresolved planes-128 STM block
+        # (route choices left to plan-time timing: the lists hold one route, these records name its steps and the alternative)
+        self._stm128 = []                                     # (list, fused step, its three launches, params, name) per planes-128 STM block
         self._upfold = []                                     # upsampled maps whose reader convs may read the source instead (_resolve_upfold)
         self.upfold_routes = {}                               # GroupNorm name of the map -> 1 folded / 0 pass (reports, tests)
-        self._fused_stats = []
+        self._fused_stats = []                                # (params block that accumulates statistics, index in the arena)
+        self._late = []                                       # steps waiting for the arena (late_step)
         self._convs = []
         self._predicted = []                                  # (layer, otvm_gram_params, slot in self.diag) of every predicted tail
         self.diag = None
@@ -1302,7 +1354,7 @@ class FramePlan:
         cands = [0] + [int(codes[i]) for i in range(n)]           # 0 = the built-in heuristic, the incumbent
         if not WAVE_TILE:                                         # (the fragment-major weights alone do not switch the one-wave tile on)
             cands = [c for c in cands if c // 16 - 1 != 9]
-        step = (self.lib.otvm_conv2d, (C.byref(p),), "conv " + name)
+        step = Step(self.lib.otvm_conv2d, (C.byref(p),), "conv " + name, True)
 
         def steps_of(c):
             p.tune = c
@@ -1327,30 +1379,19 @@ class FramePlan:
         convolution launches (0), whichever is faster on this map -- timed once per (map, batch) with the buffers holding random
         values (autotune), cached beside the conv tuner's choices; FUSE_STM_BLOCK128 = 2 or no tuner: fused, tile from the map."""
         n_logged = len(TUNE_LOG)
-        for S in self._stm128:
-            i = 0
-            while i < len(S):
-                st = S[i]
-                if not (isinstance(st[0], str) and st[0] == "stm128"):
-                    i += 1
-                    continue
-                _, fused, U, q, name = st
-
-                def steps_of(c):
-                    q.tile = c                                           # (the three launches of route 0 do not read it)
-                    return (fused,) if c else U
-                choice = _choose((-128, q.H, q.W, max(1, q.batch), q.x_ld, q.y_ld),
-                                 name + " (fused bottleneck: 0 = three launches, 1 / 2 / 3 = fused on 8x16 / 8x8 / 4x8 pixels)",
-                                 (q.H, q.W, 512, q.x_ld, 512, q.y_ld, 3, 3, 1, 1, 1),
-                                 lambda: _time_candidates(self.e, _EventClock(self.dev), steps_of, (0, 1, 2, 3) * 2, 3, warm=(0, 0)),
-                                 forced=(STM128_TILE or -1) if FUSE_STM_BLOCK128 >= 2 else None, default=None if timed else -1)
-                if choice == 0:
-                    S[i:i + 1] = U
-                    i += len(U)
-                else:
-                    q.tile = max(choice, 0)                              # (-1: the library picks from the map size)
-                    S[i] = fused
-                    i += 1
+        for S, fused, U, q, name in self._stm128:
+            def steps_of(c):
+                q.tile = c                                               # (the three launches of route 0 do not read it)
+                return (fused,) if c else U
+            choice = _choose((-128, q.H, q.W, max(1, q.batch), q.x_ld, q.y_ld),
+                             name + " (fused bottleneck: 0 = three launches, 1 / 2 / 3 = fused on 8x16 / 8x8 / 4x8 pixels)",
+                             (q.H, q.W, 512, q.x_ld, 512, q.y_ld, 3, 3, 1, 1, 1),
+                             lambda: _time_candidates(self.e, _EventClock(self.dev), steps_of, (0, 1, 2, 3) * 2, 3, warm=(0, 0)),
+                             forced=(STM128_TILE or -1) if FUSE_STM_BLOCK128 >= 2 else None, default=None if timed else -1)
+            if choice == 0:
+                _splice(S, fused, U)
+            else:
+                q.tile = max(choice, 0)                                  # (-1: the library picks from the map size)
         self._stm128 = []
         _save_choices_timed_since(n_logged)
 
@@ -1442,7 +1483,8 @@ class FramePlan:
         # algorithmic bytes: read the input once, the weights once, write the output once (+ residual read), fp32
         abytes = 4 * (x.B * x.H * x.W * w.I * (2 if in_res is not None else 1) + w.O * w.I * w.kh * w.kw
                       + x.B * Ho * Wo * w.O * (2 if residual is not None else 1))
-        S.append((self.lib.otvm_conv2d, (C.byref(p),), "conv " + wname, flops, abytes, (x, out.ch(0, _rup(w.O, 4)) if out.C >= _rup(w.O, 4) else out)))
+        S.append(Step(self.lib.otvm_conv2d, (C.byref(p),), "conv " + wname, True, flops, abytes,
+                      x, out.ch(0, _rup(w.O, 4)) if out.C >= _rup(w.O, 4) else out))
         if up_source is not None:
             assert up_source["out"].t is x.t and up_source["out"].off == x.off and stride == 1 and in_norm is None and in_res is None
             up_source["readers"].append((S, S[-1], p, x, wname))
@@ -1474,16 +1516,21 @@ class FramePlan:
         flops = 2 * x.P * w.O * 9 * w.I * x.B
         abytes = 4 * (x.B * x.P * w.I + w.O * w.I * 9 + x.B * x.P * (16 if hid_out is not None else 0) + x.B * x.P * 4)
         if fgr is not None:
-            S.append((self.lib.otvm_conv2d_head_fgr, (C.byref(p), C.byref(h), fgr[0], fgr[1]), "conv " + wname + " (+ head, F)", flops,
-                      abytes + 4 * x.B * x.P * 3, (x, hid_out if hid_out is not None else x)))
+            S.append(Step(self.lib.otvm_conv2d_head_fgr, (C.byref(p), C.byref(h), fgr[0], fgr[1]), "conv " + wname + " (+ head, F)", True,
+                          flops, abytes + 4 * x.B * x.P * 3, x, out))
             return p
-        S.append((self.lib.otvm_conv2d_head, (C.byref(p), C.byref(h)), "conv " + wname + " (+ head)", flops, abytes,
-                  (x, hid_out if hid_out is not None else x)))
+        S.append(Step(self.lib.otvm_conv2d_head, (C.byref(p), C.byref(h)), "conv " + wname + " (+ head)", True, flops, abytes, x, out))
         return p
 
-    def gn(self, S, x, name, act, out=None, residual=None, conv_p=None, res_norm=None):
+    def late_step(self, S, fn, label, args_of):
+        """A step whose arguments need the statistics arena: ``args_of(arena base, doubles per image)`` -> args, called by _bind_stats."""
+        S.append(Step(fn, None, label, late=args_of))
+        self._late.append(S[-1])
+
+    def gn(self, S, x, name, act, out=None, residual=None, conv_p=None, res_norm=None, stats_summed=False):
         """GroupNorm(32) of the raw conv output ``x``.  With ``conv_p`` (the params of the conv that produced x)
-        the statistics are accumulated in that conv's epilogue and the separate stats pass is dropped.
+        the statistics are accumulated in that conv's epilogue and the separate stats pass is dropped; ``stats_summed``: other steps
+        of the list sum them into block ``self.n_gn`` of the arena themselves.
         res_norm = (scale_ptr, shift_ptr, act): the residual is a raw GroupNorm input normalised on the fly."""
         out = x if out is None else out
         sd = self.e.sd
@@ -1491,8 +1538,9 @@ class FramePlan:
         self.n_gn += 1
         if conv_p is not None and FUSE_GN_STATS:
             self._fused_stats.append((conv_p, idx))
-        else:
-            S.append(("gn_stats", (x.ptr, x.P, x.C, x.ld), idx, (self.B, x.bs), "gn_stats " + name))
+        elif not stats_summed:
+            self.late_step(S, self.lib.otvm_gn_stats_b, "gn_stats " + name,
+                           lambda base, sbs: (x.ptr, x.P, x.C, x.ld, base + idx * 512, self.B, x.bs, sbs))
         q = L.GnApplyParams()
         q.x, q.P, q.C, q.ld = x.ptr, x.P, x.C, x.ld
         q.gamma, q.beta = sd[name + ".weight"].data_ptr(), sd[name + ".bias"].data_ptr()
@@ -1504,7 +1552,11 @@ class FramePlan:
         q.act, q.out, q.out_ld = act, out.ptr, out.ld
         q.batch, q.x_bs, q.out_bs = self.B, x.bs, out.bs
         self._keep.append(q)
-        S.append(("gn_apply", q, idx, "gn_apply " + name))
+
+        def args_of(base, sbs):
+            q.stats, q.stats_bs = base + idx * 512, sbs
+            return (C.byref(q),)
+        self.late_step(S, self.lib.otvm_gn_apply_b, "gn_apply " + name, args_of)
 
     def gn_table_step(self, S, x, gn_name, producer_p):
         """Per-channel scale / shift of GroupNorm(gn_name) over the raw conv output ``x`` (statistics from the producing
@@ -1521,8 +1573,9 @@ class FramePlan:
             producer_p.gn_scale_out, producer_p.gn_shift_out = tab.data_ptr(), tab.data_ptr() + 4 * x.C
             producer_p.gn_counter, producer_p.gn_tab_bs = cnt.data_ptr(), 2 * x.C
         else:
-            S.append(("gn_table", (x.P, x.C, sd[gn_name + ".weight"].data_ptr(), sd[gn_name + ".bias"].data_ptr(),
-                                   tab.data_ptr(), tab.data_ptr() + 4 * x.C), idx, 2 * x.C, "gn_table " + gn_name))
+            self.late_step(S, self.lib.otvm_gn_table_b, "gn_table " + gn_name,
+                           lambda base, sbs: (base + idx * 512, x.P, x.C, sd[gn_name + ".weight"].data_ptr(), sd[gn_name + ".bias"].data_ptr(),
+                                              tab.data_ptr(), tab.data_ptr() + 4 * x.C, self.B, sbs, 2 * x.C))
         return tab.data_ptr(), tab.data_ptr() + 4 * x.C, 2 * x.C
 
     def gn_then_conv(self, S, x, gn_name, gn_act, producer_p, wname, out, **kw):
@@ -1549,30 +1602,18 @@ class FramePlan:
         for conv_p, idx in self._fused_stats:
             conv_p.gn_stats = base + idx * 512
             conv_p.gn_bs = sbs
-        for key, S in self.steps.items():
-            for i, st in enumerate(S):
-                if st[0] == "gn_stats":
-                    _, a, idx, (nb, x_bs), label = st
-                    S[i] = (self.lib.otvm_gn_stats_b, a + (base + idx * 512, nb, x_bs, sbs), label)
-                elif st[0] == "gn_table":
-                    _, a, idx, nbs, label = st
-                    S[i] = (self.lib.otvm_gn_table_b, (base + idx * 512,) + a + (self.B, sbs, nbs), label)
-                elif st[0] == "ppm_add":
-                    _, a, b, label = st
-                    S[i] = (self.lib.otvm_ppm_conv_add, a + (self._ppm_stats.gn_stats + 8 * b * sbs,), label)
-                elif st[0] == "gn_apply":
-                    _, q, idx, label = st
-                    q.stats, q.stats_bs = base + idx * 512, sbs
-                    S[i] = (self.lib.otvm_gn_apply_b, (C.byref(q),), label)
+        for st in self._late:
+            st.args, st.late = st.late(base, sbs), None
+        self._late = []
 
     def upsample(self, S, x, out, add=None, norm=None):
         """norm = (scale_ptr, shift_ptr, act, table stride): x is a raw GroupNorm input, normalised per source pixel while
         resampling."""
-        S.append((self.lib.otvm_upsample_bilinear_b,
-                  (x.ptr, x.H, x.W, x.C, x.ld, 0 if norm is None else norm[0], 0 if norm is None else norm[1],
-                   0 if norm is None else norm[2], 0 if add is None else add.ptr, 0 if add is None else add.ld,
-                   out.ptr, out.H, out.W, out.ld, x.B, x.bs, 0 if add is None else add.bs, out.bs,
-                   0 if norm is None else norm[3]), "upsample"))
+        S.append(Step(self.lib.otvm_upsample_bilinear_b,
+                      (x.ptr, x.H, x.W, x.C, x.ld, 0 if norm is None else norm[0], 0 if norm is None else norm[1],
+                       0 if norm is None else norm[2], 0 if add is None else add.ptr, 0 if add is None else add.ld,
+                       out.ptr, out.H, out.W, out.ld, x.B, x.bs, 0 if add is None else add.bs, out.bs,
+                       0 if norm is None else norm[3]), "upsample"))
 
     def gn_then_upsample(self, S, x, gn_name, gn_act, producer_p, out):
         """GroupNorm + activation of the raw conv output ``x`` whose only consumer is a bilinear resampling: the apply
@@ -1613,7 +1654,8 @@ class FramePlan:
                 self._keep += [pf, u]
                 w = self.e.W[wname]
                 saved = 4 * x.B * x.P * min(src.C, w.I) * 3 // 4               # the upsampled channels are read at a quarter of the pixels
-                folded.append((self.lib.otvm_conv2d_up, (C.byref(pf), C.byref(u)), step[2] + " (+ up2x)", step[3], step[4] - saved, step[5]))
+                folded.append(Step(self.lib.otvm_conv2d_up, (C.byref(pf), C.byref(u)), step.label + " (+ up2x)", True, step.flops,
+                                   step.abytes - saved, step.src, step.dst))
             if folded is None:
                 continue
             key = (-2, src.H, src.W, max(1, src.B), src.C, src.ld) + tuple(v for r in m["readers"] for v in (r[2].Cin, r[2].Cout, r[2].act))
@@ -1623,18 +1665,25 @@ class FramePlan:
                              lambda: _time_candidates(self.e, _EventClock(self.dev), routes.get, (0, 1) * 4, 3, warm=(0, 0, 1, 1)),
                              forced=1 if FOLD_UPSAMPLE >= 2 else None, default=None if timed else 0)
             if choice:
-                at = lambda S, st: next(i for i, q in enumerate(S) if q is st)   # noqa: E731 -- (by identity: tuples of ctypes objects)
-                del m["S"][at(m["S"], m["step"])]
+                _splice(m["S"], m["step"], [])
                 for (S, step, p, x, wname), fs in zip(m["readers"], folded):
-                    S[at(S, step)] = fs
+                    _splice(S, step, [fs])
                 self.upfold_routes[m["name"]] = 1
                 for b in range(max(1, m["out"].B)):                             # nobody writes these channels any more: zeros, not
                     m["out"].torch(b).zero_()                                   # the timing's leftovers, for the stage diagnostics
         self._upfold = []
         _save_choices_timed_since(n_logged)
 
+    def ppm_conv_add(self, S, u1):
+        """The PPM channels' share of conv_up1.0 gathered into ``u1``, image by image.  The gather writes the layer's final values:
+        it also accumulates their GroupNorm sums, in the block of the arena that the gn() behind it is handed (stats_summed)."""
+        for b in range(self.B):
+            self.late_step(S, self.lib.otvm_ppm_conv_add, "ppm_conv_add",
+                           lambda base, sbs, a=(self.PPM_Z[b].data_ptr(), u1.H, u1.W, u1.img(b).ptr, u1.ld), b=b, idx=self.n_gn:
+                           a + (base + idx * 512 + 8 * b * sbs,))
+
     def maxpool(self, S, x, out):
-        S.append((self.lib.otvm_maxpool3x3s2_b, (x.ptr, x.H, x.W, x.C, x.ld, out.ptr, out.ld, x.B, x.bs, out.bs), "maxpool"))
+        S.append(Step(self.lib.otvm_maxpool3x3s2_b, (x.ptr, x.H, x.W, x.C, x.ld, out.ptr, out.ld, x.B, x.bs, out.bs), "maxpool"))
 
     # ---- network pieces
     def gn_bottleneck(self, S, x, p, planes, stride, dil, has_ds, out):
@@ -1711,7 +1760,7 @@ class FramePlan:
         q.diag = self.diag.data_ptr() + 8 * slot
         self._predicted.append((p, q, slot))
         self._keep.append(q)
-        S.append((lib.otvm_gram_f16, (C.byref(q),), "gram " + p))
+        S.append(Step(lib.otvm_gram_f16, (C.byref(q),), "gram " + p))
         tab = self.raw("gnpred_" + p, 2 * C4 * B)                        # [B][scale_eff C4 | bias_eff C4]
         cnt = self.raw("gnpredcnt_" + p, B, torch.int32)
         r = L.GnPredictParams()
@@ -1725,7 +1774,7 @@ class FramePlan:
         r.batch, r.tab_bs, r.rs_bs = B, 2 * C4, 0 if rsh is None else rnbs
         r.diag = q.diag
         self._keep.append(r)
-        S.append((lib.otvm_gn_predict, (C.byref(r),), "gn_predict " + p))
+        S.append(Step(lib.otvm_gn_predict, (C.byref(r),), "gn_predict " + p))
         cp3 = self.conv(S, t2, wname, out, in_norm=(sc, sh, RELU, nbs), residual=idt, act=RELU)
         cp3.w_scale, cp3.bias, cp3.ws_bs = tab.data_ptr(), tab.data_ptr() + 4 * C4, 2 * C4
         if rsc is not None:
@@ -1748,8 +1797,8 @@ class FramePlan:
             P = x.B * x.H * x.W
             flops = 2 * P * (x.C * 64 + 9 * 64 * 64 + 64 * 256 + (x.C * 256 if has_ds else 0))
             abytes = 4 * (P * x.C + P * 256 + x.C * 64 + 9 * 64 * 64 + 64 * 256 + (x.C * 256 if has_ds else 0))
-            S.append((self.lib.otvm_stm_bottleneck_f16x3, (C.byref(q),), "conv " + p + " (fused bottleneck)", flops, abytes,
-                      (x, out.ch(0, 256) if out.C > 256 else out)))
+            S.append(Step(self.lib.otvm_stm_bottleneck_f16x3, (C.byref(q),), "conv " + p + " (fused bottleneck)", True, flops, abytes,
+                          x, out.ch(0, 256) if out.C > 256 else out))
             return
         c1, c2, c3 = W[p + ".conv1"], W[p + ".conv2"], W.get(p + ".conv3")
         fuse128 = (FUSE_STM_BLOCK128 and self.e.precision == L.PREC_F16X3 and self.e.conv_precision == L.PREC_F16X3 and planes == 128
@@ -1776,11 +1825,11 @@ class FramePlan:
             P = x.B * x.H * x.W
             flops = 2 * P * (512 * 128 + 9 * 128 * 128 + 128 * 512)
             abytes = 4 * (P * 512 * 2 + 512 * 128 * 2 + 9 * 128 * 128)
-            fused = (self.lib.otvm_stm_bottleneck_f16x3, (C.byref(q),), "conv " + p + " (fused bottleneck)", flops, abytes,
-                     (x, out.ch(0, 512) if out.C > 512 else out))
-            # resolved by _resolve_stm128 (timed at plan time): either `fused` or the launches of `U` take this place
-            S.append(("stm128", fused, U, q, p))
-            self._stm128.append(S)
+            fused = Step(self.lib.otvm_stm_bottleneck_f16x3, (C.byref(q),), "conv " + p + " (fused bottleneck)", True, flops, abytes,
+                         x, out.ch(0, 512) if out.C > 512 else out)
+            # resolved by _resolve_stm128 (timed at plan time): `fused` keeps this place or the launches of `U` take it
+            S.append(fused)
+            self._stm128.append((S, fused, U, q, p))
 
     def stm_trunk(self, S, stem_out, e, tag):
         """maxpool + res2/res3/res4 (BN folded) of an STM encoder.  Returns r4, r3, r2."""
@@ -1874,7 +1923,7 @@ class FramePlan:
         self.L4 = self.buf("L4", H4, W4, 4)
         self.conv(S, pm, d + "pred", self.L4, pad=1, in_relu=1)
         for b in range(self.B):
-            S.append((lib.otvm_upsample4_softmax3, (self.L4.img(b).ptr, H4, W4, self.L4.ld, self.PROBS_B[b].data_ptr()), "up4softmax"))
+            S.append(Step(lib.otvm_upsample4_softmax3, (self.L4.img(b).ptr, H4, W4, self.L4.ld, self.PROBS_B[b].data_ptr()), "up4softmax"))
         self.steps["segment_b"] = S
 
         # ---------------- FBA encoder (FBA/models.py:251-269)
@@ -1912,8 +1961,8 @@ class FramePlan:
         self.POOL_B = self.raws("ppm_pool", 50 * 2048)
         self.POOL_WS_B = self.raws("ppm_ws", int(lib.otvm_ppm_pool_ws_bytes(H8, 2048)) // 4)
         for b in range(self.B):                          # (three small launches per image: not batched)
-            S.append((lib.otvm_ppm_pool, (conv5.img(b).ptr, H8, W8, 2048, conv5.ld, self.POOL_B[b].data_ptr(),
-                                          self.POOL_WS_B[b].data_ptr()), "ppm_pool"))
+            S.append(Step(lib.otvm_ppm_pool, (conv5.img(b).ptr, H8, W8, 2048, conv5.ld, self.POOL_B[b].data_ptr(),
+                                              self.POOL_WS_B[b].data_ptr()), "ppm_pool"))
         if FUSE_PPM_HEAD and self.e.W[de + "ppm.0.1"].I_pad == 2048 and self.e.W[de + "ppm.0.1"].O == 256:
             # conv + bias + GroupNorm + LeakyReLU of the four pooled maps in ONE launch (16 launches as library calls)
             sd = self.e.sd
@@ -1928,7 +1977,7 @@ class FramePlan:
                     hp.gamma[i], hp.beta[i] = sd[de + "ppm.%d.2.weight" % i].data_ptr(), sd[de + "ppm.%d.2.bias" % i].data_ptr()
                     hp.out[i] = ys[i].img(b).ptr
                 self._keep.append(hp)
-                S.append((lib.otvm_ppm_head, (C.byref(hp),), "ppm_head"))
+                S.append(Step(lib.otvm_ppm_head, (C.byref(hp),), "ppm_head"))
             self._ppm_algebra = ppm_alg
             if not self._ppm_algebra:
                 for i, y in enumerate(ys):
@@ -1952,14 +2001,10 @@ class FramePlan:
             for b in range(self.B):
                 yp = (C.c_void_p * 4)(*[y.img(b).ptr for y in ys])
                 self._keep.append(yp)
-                S.append((lib.otvm_ppm_conv_z, (yp, ys[0].ld, self.e.W_ppm.data_ptr(), self.PPM_Z[b].data_ptr()), "ppm_conv_z"))
+                S.append(Step(lib.otvm_ppm_conv_z, (yp, ys[0].ld, self.e.W_ppm.data_ptr(), self.PPM_Z[b].data_ptr()), "ppm_conv_z"))
             self.conv(S, self.PPMCAT.ch(0, 2048), de + "conv_up1.0.main", u1, pad=1)
-            for b in range(self.B):
-                S.append(("ppm_add", (self.PPM_Z[b].data_ptr(), H8, W8, u1.img(b).ptr, u1.ld), b, "ppm_conv_add"))
-            # the gather writes the layer's final values: it also accumulates their GroupNorm sums (bound in _bind_stats)
-            import types
-            self._ppm_stats = types.SimpleNamespace(gn_stats=0, gn_bs=0)
-            self.gn(S, u1, de + "conv_up1.1", LEAKY, conv_p=self._ppm_stats)
+            self.ppm_conv_add(S, u1)
+            self.gn(S, u1, de + "conv_up1.1", LEAKY, stats_summed=True)
         else:
             cp = self.conv(S, self.PPMCAT, de + "conv_up1.0", u1, pad=1)
             self.gn(S, u1, de + "conv_up1.1", LEAKY, conv_p=cp)
@@ -1986,9 +2031,9 @@ class FramePlan:
             hid_d = self.HID_D = self.buf("hid_d", Hp, Wp, 16)
             self.conv(S, h32, de + "conv_up4.2", hid_d, pad=1, act=LEAKY)
             for b in range(self.B):
-                S.append((lib.otvm_fba_head,
-                          (hid_d.img(b).ptr, hid_d.ld, sd[de + "conv_up4.4.weight"].data_ptr(), sd[de + "conv_up4.4.bias"].data_ptr(), 7,
-                           img.img(b).ptr, img.ld, P, self.D80.ch(72, 1).img(b).ptr, self.D80.ld, 0, 0, 0), "fba_head7"))
+                S.append(Step(lib.otvm_fba_head,
+                              (hid_d.img(b).ptr, hid_d.ld, sd[de + "conv_up4.4.weight"].data_ptr(), sd[de + "conv_up4.4.bias"].data_ptr(), 7,
+                               img.img(b).ptr, img.ld, P, self.D80.ch(72, 1).img(b).ptr, self.D80.ld, 0, 0, 0), "fba_head7"))
         # ---------------- refinement (FBA/models.py:417-435)
         rf = "NET.refine."
         r0 = self.buf("r0", Hp, Wp, 64)
@@ -2042,9 +2087,9 @@ class FramePlan:
                         img.img(b).ptr, img.ld, P, self.ALPHA_P_B[b].data_ptr(), 1, self.TRI_P_B[b].data_ptr(),
                         SM.ch(16, 8).img(b).ptr, SM.ld)
                 if self.fgr:
-                    S.append((lib.otvm_fba_head_fgr, args + (self.FGR_P_B[b].data_ptr(),), "fba_head10 (+ F)"))
+                    S.append(Step(lib.otvm_fba_head_fgr, args + (self.FGR_P_B[b].data_ptr(),), "fba_head10 (+ F)"))
                 else:
-                    S.append((lib.otvm_fba_head, args, "fba_head10"))
+                    S.append(Step(lib.otvm_fba_head, args, "fba_head10"))
             self.steps["fba_tail%d" % par] = S
 
         # ---------------- STM memorize (STM.py:201-228); key/value convs are bound to a slot at run time
@@ -2067,68 +2112,32 @@ class FramePlan:
         torch.cuda.graph; ``tstream`` = the torch stream object when it is not the current one): ~300 kernel launches per
         frame become a handful of graph launches (host time per frame 6.8 -> 0.9 ms at 480p; no throughput change, every
         measured configuration is GPU-bound).  Opt-in: OTVM_GRAPHS=1 or engine.use_graphs = True."""
-        prof = self.e.prof
+        prof, steps = self.e.prof, self.steps[key]
         nc = self._n_conv.get(key)
         if nc is None:
-            nc = self._n_conv[key] = sum(1 for st in self.steps[key] if not isinstance(st[0], str) and st[2].startswith("conv "))
+            nc = self._n_conv[key] = sum(st.conv for st in steps)
         self.e.conv_calls += nc
-        if prof is None and self.e.check_level >= 3:
-            # first run of a new checkpoint: scan the input and the output of every convolution
-            for st in self.steps[key]:
-                if isinstance(st[0], str):
-                    continue                              # (fork / join markers: one serial stream here)
-                if st[2].startswith("conv "):
-                    self.e.guard(st[5][0], "input of " + st[2], stream)
-                rc = st[0](*st[1], stream)
-                if rc != 0:
-                    L.check(rc, st[2])
-                if st[2].startswith("conv "):
-                    self.e.scan_now(st[5][1], "output of " + st[2], stream)
+        level3 = self.e.check_level >= 3
+        if prof is not None or level3:
+            # bench.py's roofline leg: HIP events around every conv launch; else the first run of a new checkpoint: every conv scanned
+            _issue(steps, stream, self.e, prof, scan=level3, guard_in=level3)
             return
-        if prof is None:
-            if graphs_wanted(self.e.use_graphs, self.P):
-                g = self.graphs.get(key)
-                if g is None and self._graph_warm.get(key):
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, capture_error_mode="thread_local"):   # other threads (the IO pipeline) keep issuing copies
-                        self._launch(self.steps[key], torch.cuda.current_stream(self.dev))
-                    self.graphs[key] = g
-                if g is not None:
-                    if tstream is None:
+        if graphs_wanted(self.e.use_graphs, self.P):
+            g = self.graphs.get(key)
+            if g is None and self._graph_warm.get(key):
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, capture_error_mode="thread_local"):   # other threads (the IO pipeline) keep issuing copies
+                    _issue(steps, torch.cuda.current_stream(self.dev).cuda_stream)
+                self.graphs[key] = g
+            if g is not None:
+                if tstream is None:
+                    g.replay()
+                else:
+                    with torch.cuda.stream(tstream):
                         g.replay()
-                    else:
-                        with torch.cuda.stream(tstream):
-                            g.replay()
-                    return
-                self._graph_warm[key] = True              # first use: direct launches (module loading, warm-up)
-            self._launch(self.steps[key], tstream if tstream is not None else torch.cuda.current_stream(self.dev), stream)
-            return
-        # instrumented pass (bench.py roofline leg): HIP events around every conv launch, on this stream
-        for st in self.steps[key]:
-            if isinstance(st[0], str):
-                continue
-            if st[2].startswith("conv "):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                rc = st[0](*st[1], stream)
-                e1.record()
-                prof.append((st[2], st[3], e0, e1, st[4]))
-            else:
-                rc = st[0](*st[1], stream)
-            if rc != 0:
-                L.check(rc, st[2])
-
-    def _launch(self, steps, tmain, handle=None):
-        """Issue ``steps`` on the torch stream ``tmain`` (raw handle ``handle``).  Every step must be a bound library call by now:
-        a string marker left in a list (a step _bind_stats did not rebind) is an error, not something to skip."""
-        handle = tmain.cuda_stream if handle is None else handle
-        for st in steps:
-            f = st[0]
-            if isinstance(f, str):
-                raise RuntimeError("otvm_amd: unbound step %r in a launch list" % (f,))
-            rc = f(*st[1], handle)
-            if rc != 0:
-                L.check(rc, st[2])
+                return
+            self._graph_warm[key] = True                  # first use: direct launches (module loading, warm-up)
+        _issue(steps, stream)
 
     def new_slot(self):
         e = self.e
@@ -2221,18 +2230,8 @@ class FramePlan:
             self.conv(S, self.r4m, "trimap.model.KV_M_r4.Value", slot["v"], pad=1)
             self.tune_convs(self._convs[n0:])                  # shapes timed at plan time (autotune): cache hits
             slot["kv_steps"] = S
-        prof = self.e.prof
         self.e.conv_calls += len(slot["kv_steps"])
-        for st in slot["kv_steps"]:
-            if prof is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            L.check(st[0](*st[1], stream), st[2])
-            if prof is not None:
-                e1.record()
-                prof.append((st[2], st[3], e0, e1, st[4]))
-            if prof is None and self.e.check_level >= 3:
-                self.e.scan_now(st[5][1], "output of " + st[2], stream)
+        _issue(slot["kv_steps"], stream, self.e, self.e.prof, scan=self.e.check_level >= 3)      # (the input, r4m, is not guarded)
         self.e.guard(slot["k"], "memorised key", stream, slot["frame"])
         self.e.guard(slot["v"], "memorised value", stream, slot["frame"])
         if "packed_b" in slot:

@@ -554,6 +554,51 @@ def test_graph_replay_equals_direct_launches(synth_sd):
     assert torch.equal(outs[0]["alpha"], outs[1]["alpha"]) and torch.equal(outs[0]["trimap"], outs[1]["trimap"])
 
 
+def test_instrumented_and_scanned_passes_launch_what_the_direct_pass_launches(synth_sd):
+    """The three ways a launch list is issued from Python -- direct launches, the instrumented pass (engine.prof) and the pass at
+    check level 3 -- on one 96x128 clip of three frames, all on the launch stream alone: equal bits, equal convolution counts per
+    frame, one profile entry per counted convolution."""
+    from otvm_amd import helpers
+    from otvm_amd.synth_data import synthetic_clip
+    from otvm_amd.video import run_video_matte
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    H, W, T = 96, 128, 3
+    cfg = helpers.default_cfg()
+    frames, tri = synthetic_clip(H, W, T, seed=93)
+
+    def run(mode):
+        m = helpers.get_model_alpha(cfg, helpers.get_model_trimap(cfg, "Test", 12), "Test", 12)
+        m.load_state_dict(synth_sd, strict=True)
+        m = m.cuda().eval()
+        eng = m._get_engine()
+        eng.use_side_stream, eng.use_graphs = False, False
+        eng.plan(H, W)                                           # built (and tuned) before anything is counted
+        if mode == "prof":
+            eng.prof = []
+        elif mode == "level3":
+            eng.check_level = 3
+        growth, profiled, last = [], [], [eng.conv_calls]
+
+        def on_frame(i, alpha, u8, out):
+            growth.append(eng.conv_calls - last[0])
+            last[0] = eng.conv_calls
+            profiled.append(0 if eng.prof is None else sum(1 for e in eng.prof if e[0].startswith("conv ")))
+        res = run_video_matte(m, frames, trimap=tri, skip=2, max_num=3, on_frame=on_frame)
+        return res, growth, profiled, eng.prof
+    plain, g_plain, _, _ = run("plain")
+    prof, g_prof, n_prof, entries = run("prof")
+    lvl3, g_lvl3, _, _ = run("level3")
+    print("convolution launches per frame:", g_plain, "profile entries after each frame:", n_prof)
+    assert len(g_plain) == T and all(g > 0 for g in g_plain) and g_plain == g_prof == g_lvl3
+    for t in range(T):
+        for other in (prof, lvl3):
+            assert torch.equal(plain["alpha"][t], other["alpha"][t]) and torch.equal(plain["trimap"][t], other["trimap"][t]), t
+    assert n_prof == [sum(g_prof[:t + 1]) for t in range(T)]
+    assert all(len(e) == 5 and (e[0].startswith("conv ") or e[0] == "memory_read") for e in entries)
+    assert any(e[0] == "memory_read" for e in entries)
+
+
 def test_autotuned_plan_matches_heuristic_plan(synth_sd, monkeypatch):
     """The plan-time autotuner (engine.AUTOTUNE) only re-orders fp32 sums: a clip matted with tuned configurations stays
     within the parity bound of the same clip matted with the built-in heuristic, two engines of one process share the

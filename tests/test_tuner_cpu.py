@@ -60,7 +60,7 @@ def test_conv_protocol_launch_sequence_and_minimum():
     """Conv shape with the candidates [0, 35, 51]: 3 launches of code 0 thrown away, then for each of 0, 35, 51, 0 one untimed
     launch and three timed ones -- 3 + 4 * 4 = 19 conv launches; the incumbent's time is the smaller of its two measurements."""
     log, code = [], [None]
-    step = (recorder(log, lambda: code[0]), ("params",), "conv layer")
+    step = engine.Step(recorder(log, lambda: code[0]), ("params",), "conv layer", True)
 
     def steps_of(c):
         code[0] = c
@@ -78,8 +78,8 @@ def test_stm128_protocol_launch_sequence_and_minimum():
     """Planes-128 block: 2 untimed repetitions of route 0 (three launches each), then 0,1,2,3,0,1,2,3 at 3 repetitions with
     nothing in between -- 42 conv launches; the result is the minimum, neither the last measurement nor the mean."""
     log = []
-    U = [(recorder(log, "u%d" % i), (), "conv block.conv%d" % i) for i in (1, 2, 3)]
-    fused = (recorder(log, "f"), (), "conv block (fused bottleneck)")
+    U = [engine.Step(recorder(log, "u%d" % i), (), "conv block.conv%d" % i, True) for i in (1, 2, 3)]
+    fused = engine.Step(recorder(log, "f"), (), "conv block (fused bottleneck)", True)
     eng = SimpleNamespace(conv_calls=0)
     clock = FakeClock(log, [1.0, 5.0, 3.0, 4.0, 2.0, 4.0, 6.0, 4.5])
     ms = engine._time_candidates(eng, clock, lambda c: U if c == 0 else (fused,), (0, 1, 2, 3, 0, 1, 2, 3), 3, warm=(0, 0))
@@ -95,8 +95,9 @@ def test_upfold_protocol_launch_sequence(readers):
     """Folded upsampling: 2 untimed repetitions of each route, then 0,1,0,1,0,1,0,1 at 3 repetitions -- 28 conv launches per
     reader (the upsampling pass of route 0 is launched with them and is not a conv)."""
     log = []
-    r0 = [(recorder(log, "up"), (), "upsample")] + [(recorder(log, "r%d" % i), (), "conv reader%d" % i) for i in range(readers)]
-    r1 = [(recorder(log, "R%d" % i), (), "conv reader%d (+ up2x)" % i) for i in range(readers)]
+    r0 = [engine.Step(recorder(log, "up"), (), "upsample")]
+    r0 += [engine.Step(recorder(log, "r%d" % i), (), "conv reader%d" % i, True) for i in range(readers)]
+    r1 = [engine.Step(recorder(log, "R%d" % i), (), "conv reader%d (+ up2x)" % i, True) for i in range(readers)]
     routes = {0: r0, 1: r1}
     eng = SimpleNamespace(conv_calls=0)
     clock = FakeClock(log, [3.0, 2.0, 2.5, 2.2, 2.9, 1.9, 2.6, 2.1])
@@ -118,8 +119,8 @@ def test_every_launch_is_checked(monkeypatch):
         if rc != 0:
             raise RuntimeError(what)
     monkeypatch.setattr(L, "check", check)
-    bad = (lambda *a: 7, (), "conv broken")
-    good = (recorder(log, "g"), (), "conv fine")
+    bad = engine.Step(lambda *a: 7, (), "conv broken", True)
+    good = engine.Step(recorder(log, "g"), (), "conv fine", True)
     eng = SimpleNamespace(conv_calls=0)
     with pytest.raises(RuntimeError):
         engine._time_candidates(eng, FakeClock(log, [1.0, 1.0]), lambda c: (good, bad) if c else (good,), (0, 1), 3, warm=(0,))
@@ -222,12 +223,12 @@ def stm128_plan(log, monkeypatch, per_rep):
     monkeypatch.setattr(engine, "_EventClock", lambda dev: clock)
     q = L.StmBottleneckParams()
     q.H, q.W, q.batch, q.x_ld, q.y_ld = 12, 16, 1, 512, 512
-    U = [(recorder(log, "u%d" % i), (), "conv res3.1.conv%d" % i) for i in (1, 2, 3)]
-    fused = (recorder(log, lambda: "f%d" % q.tile), (ctypes.byref(q),), "conv res3.1 (fused bottleneck)")
-    before, after = ("before", (), "maxpool"), ("after", (), "conv next")
-    S = [before, ("stm128", fused, U, q, "res3.1"), after]
+    U = [engine.Step(recorder(log, "u%d" % i), (), "conv res3.1.conv%d" % i, True) for i in (1, 2, 3)]
+    fused = engine.Step(recorder(log, lambda: "f%d" % q.tile), (ctypes.byref(q),), "conv res3.1 (fused bottleneck)", True)
+    before, after = engine.Step("before", (), "maxpool"), engine.Step("after", (), "conv next", True)
+    S = [before, fused, after]
     plan = fake_plan(None)
-    plan._stm128 = [S]
+    plan._stm128 = [(S, fused, U, q, "res3.1")]
     return plan, S, U, fused, q, before, after
 
 

@@ -1,12 +1,17 @@
-import sys, os, torch
-sys.path.insert(0, "/root/repo")
-import bench
+"""List the separate GroupNorm statistics / apply passes left in the 1080p plan (list key, step label)."""
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench  # noqa: E402
+
 dev = torch.device("cuda", 0)
 model, _ = bench.build_model(dev)
 eng = model._get_engine()
 plan = eng.plan(1080, 1920, 1)
 for key, S in plan.steps.items():
     for st in S:
-        lab = st[2] if isinstance(st[2], str) else str(st[-1])
-        if "gn_apply" in lab or "gn_stats" in lab:
-            print(key, lab)
+        if "gn_apply" in st.label or "gn_stats" in st.label:
+            print(key, st.label)
