@@ -274,6 +274,13 @@ def _issue(steps, stream, eng=None, prof=None, scan=False, guard_in=False):
                 eng.scan_now(st.dst, "output of " + st.label, stream)
 
 
+def _mark(stream):
+    """A new event, recorded on the torch stream ``stream``."""
+    ev = torch.cuda.Event()
+    ev.record(stream)
+    return ev
+
+
 def _splice(S, old, new):
     """Replace the step ``old`` of the launch list S -- found by identity -- by the steps ``new`` (none, one or several)."""
     for i, st in enumerate(S):
@@ -414,6 +421,74 @@ def bank_update(bank, new, first_frame, memorize, max_memory_num, anchor=False):
     return nb, released
 
 
+class Pending:
+    """The deferred memorize of a finished frame (HipEngine.pending): its slot, where the frame is held, the policy's arguments."""
+    __slots__ = ("slot", "plan", "par", "first_frame", "memorize", "max_memory_num", "anchor")
+
+    def __init__(self, slot, plan, par, first_frame, memorize, max_memory_num, anchor):
+        self.slot, self.plan, self.par, self.first_frame = slot, plan, par, first_frame
+        self.memorize, self.max_memory_num, self.anchor = memorize, max_memory_num, anchor
+
+    def apply(self, bank):                                    # the bank policy for this memorize: (bank, released slots)
+        return bank_update(bank, self.slot, self.first_frame, self.memorize, self.max_memory_num, self.anchor)
+
+
+def early_read_split(bank, pend):
+    """(old, fresh): the bank the next read visits -- ``bank`` once the deferred memorize ``pend`` has run -- cut into the slots that are
+    resident already and the one ``pend`` is about to fill (none if the policy drops it at once)."""
+    nb = list(bank) if pend is None else pend.apply(bank)[0]
+    return [s for s in nb if pend is None or s is not pend.slot], [s for s in nb if pend is not None and s is pend.slot]
+
+
+class SplitRead:
+    """A memory read in two parts (FramePlan.memory_read_begin / _fresh / _merge): their slots, the partials' workspaces, how many are done."""
+    __slots__ = ("old", "fresh", "np_cap", "done", "ws")
+
+    def __init__(self, old, fresh, np_cap, done, ws):
+        self.old, self.fresh, self.np_cap, self.done, self.ws = old, fresh, np_cap, done, ws
+
+
+class _FrameCall:
+    """What the stages of one HipEngine._frame_batch call share; every field is set where its value is made."""
+    __slots__ = ("B", "H", "W", "u8", "rgb", "ins", "lab", "pl", "outs", "main", "stream", "first_frame", "no_segment", "frame_id",
+                 "par", "pps", "train")
+
+
+GO_ON, RECOMPUTE, DROP_RECOMPUTE, WARN_SUSPECT = "go on", "recompute", "drop plans and recompute", "warn suspect"
+
+
+def retry_decision(verdict, first_frame, rechecks, predict_off, predicted):
+    """What the conditioning guard of the predicted GroupNorm statistics (GN_PREDICT_KAPPA_*) asks of the frame just issued, on a plan
+    with ``predicted`` layers or without: ``predict_off`` = engine.gn_predict_off BEFORE this frame's predict_check, ``verdict`` = what
+    the check said, ``rechecks`` = recomputations left.  A clip's first frame is checked before it is returned and computed again if a
+    layer had to change its route (the bank is empty there: the call is repeatable); later frames are watched without synchronising."""
+    if not predicted:
+        return GO_ON
+    if predict_off:   # the guard tripped in the middle of the previous clip, this clip's first frame ran on a plan that still predicts
+        return DROP_RECOMPUTE if first_frame else GO_ON
+    if not first_frame:
+        return WARN_SUSPECT if verdict == "off" else GO_ON
+    if verdict == "ok" or rechecks <= 0:
+        return GO_ON
+    return DROP_RECOMPUTE if verdict == "off" else RECOMPUTE      # ("off": rebuilt without the predicted tails)
+
+
+def refuse_frame_args(a_l, fg_l, bg_l, tri_gt_l, first_frame, keyframe, labels, max_memory_num, train):
+    """The frame step's refusals that need nothing but its arguments (no device work)."""
+    B = len(a_l)
+    if not (len(fg_l) == len(bg_l) == len(tri_gt_l) == B) or B < 1:
+        raise ValueError("otvm_amd: a / fg / bg / tri_gt lists must have the same length")
+    if keyframe or labels is not None:
+        if B > 1 or train is not None:
+            raise NotImplementedError("otvm_amd: keyframe / labels apply to a single sequence (not to lock-step batches)")
+        if labels is not None and first_frame:
+            raise ValueError("otvm_amd: labels correct a propagated trimap; a first frame takes its trimap as tri_gt")
+        if keyframe and labels is None and tri_gt_l[0] is None:
+            raise ValueError("otvm_amd: keyframe=True needs the frame's trimap as tri_gt")
+        if max_memory_num < 2:
+            raise ValueError("otvm_amd: keyframe / labels need max_memory_num >= 2 (a bank of %d slot(s) holds no anchors)" % max_memory_num)
+
+
 # name -> (kernel family, otvm_conv_params.precision).  "f16" (round 5) is a LABELLED reduced-precision mode: the f16x3 kernels,
 # weight formats and plans with ONE MFMA pass on fp16-rounded operands in the implicit-GEMM and patch kernels (include/otvm_hip.h,
 # OTVM_PREC_F16); never a default, not covered by the 1e-3 contract -- bench.py --precision f16 reports its error next to its speed
@@ -543,9 +618,7 @@ class HipEngine:
         self.conv_calls = 0          # convolution launches issued by this engine (plan steps marked conv, tuner launches included)
         self.last_T_read = 0
         self.parity = 0
-        self.side = None
-        self.side2 = None
-        import os
+        self.side = self.side2 = None
         self.use_side_stream = os.environ.get("OTVM_SIDE_STREAM", "1") != "0"
         # f16x3 splits fp32 operands into fp16 halves: an activation beyond fp16's range (|x| >= 65504) becomes inf and
         # then NaN, silently, and would live on in the recurrent memory bank.  OTVM_CHECK_FINITE=1 checks every frame's
@@ -561,7 +634,7 @@ class HipEngine:
         self.guard_flag = torch.full((1,), GUARD_CLEAR, dtype=torch.int32, device=self.dev)
         self._guard_host = torch.full((1,), GUARD_CLEAR, dtype=torch.int32).pin_memory()
         self._guard_ev = None
-        self._guard_what = {}
+        self._pp_proto = None        # otvm_preprocess parameter block with the normalisation constants filled in (_preprocess_blocks)
         self.use_graphs = USE_GRAPHS
         self.gn_predict_off = False   # set by predict_check: the plans are (re)built without the predicted GroupNorm tails
         self.gn_predict_log = []      # (layer, kappa, action) of every intervention of the conditioning guard
@@ -606,9 +679,6 @@ class HipEngine:
             L.check(self.lib.otvm_pack_wave_weight_f16x3(cw.w_hi.data_ptr(), cw.w_lo.data_ptr(), O_pad, cw.K_pad,
                                                          cw.w_wfrag.data_ptr(), self._stream()), "pack_wave_weight")
         return cw.w_wfrag
-
-    def _gram_tables(self, cw):
-        return gram_tables(self.lib, cw)
 
     def _fold_bn(self, bn):
         sd = self.sd
@@ -668,7 +738,7 @@ class HipEngine:
             for name, cw in list(self.W.items()):
                 if (name.startswith("NET.encoder.layer") and name.endswith(".conv3") and cw.kh == 1 and cw.kw == 1 and cw.bias is None
                         and cw.I % 64 == 0 and cw.O % 32 == 0 and cw.I_pad == cw.I):
-                    self.GP[name] = self._gram_tables(cw)
+                    self.GP[name] = gram_tables(self.lib, cw)
         # Encoder_M stem: conv1_h(hid16) + conv1(rgb) + conv1_m(p_un) + conv1_o(p_fg) + conv1_a(alpha) (STM.py:63-66)
         e = "trimap.model.Encoder_M."
         wcat = torch.cat([sd[e + "conv1_h.weight"], sd[e + "conv1.weight"], sd[e + "conv1_m.weight"],
@@ -736,8 +806,7 @@ class HipEngine:
                 self._guard_raise(v)
         if self._guard_ev is None and self.frame_counter % 8 == 0:
             self._guard_host.copy_(self.guard_flag, non_blocking=True)
-            self._guard_ev = torch.cuda.Event()
-            self._guard_ev.record(torch.cuda.current_stream(self.dev))
+            self._guard_ev = _mark(torch.cuda.current_stream(self.dev))
 
     # ------------------------------------------------------------------ conditioning guard of the predicted GroupNorm statistics
     def _predict_verdict(self, pl, words):
@@ -789,9 +858,7 @@ class HipEngine:
             if self._diag_host is None:
                 self._diag_host = torch.zeros(2 * 64, dtype=torch.int32).pin_memory()
             self._diag_host.copy_(pl.diag, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(self.dev))
-            self._diag_ev = (ev, pl)
+            self._diag_ev = (_mark(torch.cuda.current_stream(self.dev)), pl)
         return verdict
 
     def _drop_plans(self):
@@ -799,8 +866,7 @@ class HipEngine:
         torch.cuda.synchronize(self.dev)
         self.plans.clear()
         self.bank, self.free_slots, self.pending = [], [], None
-        self.ev_dec = None
-        self.last_plan = None
+        self.ev_dec = self.last_plan = None
 
     # ------------------------------------------------------------------ plans
     def plan(self, H, W, B=1):
@@ -817,9 +883,6 @@ class HipEngine:
         self.free_slots.extend(self.bank)
         self.bank = []
 
-    def _vec3(self, key):
-        return [float(x) for x in self.sd[key].flatten().tolist()]
-
     def frame(self, *args, **kw):
         # the raw launches below go to torch's current stream of self.dev: make that device current for the call (a model
         # on cuda:N called without torch.cuda.set_device(N) would otherwise launch into another device's context)
@@ -834,13 +897,11 @@ class HipEngine:
                dilate_kernel=None, frame_id=None, cls_override=None, frames_rgb=False, inputs_ready=None, keyframe=False,
                labels=None):
         """One call of EvalModel.forward (reference models/alpha/model.py:391-512) on the HIP path.
-
-        a [1,1,1,H,W] in [0,1]; fg, bg [1,1,3,H,W] BGR 0..255; tri_gt [1,1,3,H,W] or None.
-        Extension: fg / bg may be the decoded uint8 images themselves, [H,W,3] interleaved (BGR, or RGB with
-        ``frames_rgb``): the preprocess kernel reads them directly (same arithmetic as ``.float()`` + permute).
-        inputs_ready: True = a / fg / bg are device tensors whose contents are complete (nothing still in flight writes
-        them); a torch.cuda.Event = complete once that event has fired; None = unknown (ordered after everything issued on
-        the launch stream so far).  Only matters for how early the query encoder may start.
+        a [1,1,1,H,W] in [0,1]; fg, bg [1,1,3,H,W] BGR 0..255; tri_gt [1,1,3,H,W] or None.  Extension: fg / bg may be the decoded uint8
+        images themselves, [H,W,3] interleaved (BGR, or RGB with ``frames_rgb``): the preprocess kernel reads them directly (same
+        arithmetic as ``.float()`` + permute).  inputs_ready: True = a / fg / bg are device tensors whose contents are complete (nothing
+        still in flight writes them); a torch.cuda.Event = complete once that event has fired; None = unknown (ordered after everything
+        issued on the launch stream so far); only matters for how early the query encoder may start.
         keyframe / labels: re-anchoring a clip on a later frame (see _frame_batch).
         Returns the reference's 5-tuple (scaled_imgs, preds_trimap, tri_gt, preds_alpha, scaled_gts)."""
         return self._frame_batch([a], [fg], [bg], [tri_gt], first_frame, last_frame, memorize, max_memory_num, dilate_kernel,
@@ -850,40 +911,85 @@ class HipEngine:
     def _frame_batch(self, a_l, fg_l, bg_l, tri_gt_l, first_frame=False, last_frame=False, memorize=False, max_memory_num=2,
                      dilate_kernel=None, frame_id=None, cls_override=None, frames_rgb=False, inputs_ready=None, train=None,
                      _recheck=2, keyframe=False, labels=None):
-        """The same frame step for B independent sequences in LOCK-STEP (round 3): lists of B inputs of one resolution, one
-        memory schedule (first_frame / last_frame / memorize / max_memory_num apply to all), per-sequence banks.  Every
-        (train: buffers of the training-mode forward, otvm_amd/train.py -- the heads' full outputs and the raw logits are
-        written there as well, and frame 0 memorises the ground-truth trimap.)  Every
-        layer is ONE launch over the B images (otvm_conv_params.batch, otvm_gn_*_b, ...): the weights are read once, and
-        the small maps of the encoders -- too few tiles for 256 CUs from one image -- fill the chip.  Each image is computed
-        exactly as a batch-1 call computes it (same tiles, same summation order).  Returns a list of B 5-tuples.
-        Two opt-in extensions of the reference's frame step, single sequence only (the reference consumes a trimap on the first
-        frame alone, alpha/model.py:425-443):
-          keyframe=True with a tri_gt on a later frame -- a FULL KEYFRAME: the padded trimap is the network's trimap input exactly
-            as on a first frame (otvm_pad_trimap), the STM segment is not run (no query encoder, no memory read: last_T_read
-            == 0), the bank is NOT reset, and the slot this frame memorises is an anchor (bank_update);
-          labels = uint8 [H,W] map (0 bg, 1 unknown, 2 fg, 255 unlabelled) on a later frame -- a CORRECTION: the steady route,
-            with otvm_trimap_apply_labels between the STM decoder's softmax and the encoding; with keyframe=True its slot is
-            an anchor as well."""
-        dev, lib = self.dev, self.lib
-        f32 = torch.float32
-        B = len(a_l)
-        if not (len(fg_l) == len(bg_l) == len(tri_gt_l) == B) or B < 1:
-            raise ValueError("otvm_amd: a / fg / bg / tri_gt lists must have the same length")
+        """The same frame step for B independent sequences in LOCK-STEP: lists of B inputs of one resolution, one memory schedule
+        (first_frame / last_frame / memorize / max_memory_num apply to all), per-sequence banks.  Every layer is ONE launch over the B
+        images (otvm_conv_params.batch, otvm_gn_*_b, ...): the weights are read once, and the small maps of the encoders -- too few tiles
+        for 256 CUs from one image -- fill the chip.  Each image is computed exactly as a batch-1 call computes it (same tiles, same
+        summation order).  Returns a list of B 5-tuples.  train: buffers of the training-mode forward (otvm_amd/train.py) -- the heads'
+        full outputs and the raw logits are written there as well, and frame 0 memorises the ground-truth trimap.
+        Two opt-in extensions of the reference's frame step, single sequence only (the reference consumes a trimap on the first frame
+        alone, alpha/model.py:425-443; DESIGN.md, Keyframe trimaps):
+          keyframe=True with a tri_gt on a later frame -- a FULL KEYFRAME: the padded trimap is the network's trimap input exactly as on
+            a first frame, the STM segment is not run (last_T_read == 0), the bank is NOT reset, the slot it memorises is an anchor;
+          labels = uint8 [H,W] map (0 bg, 1 unknown, 2 fg, 255 unlabelled) on a later frame -- a CORRECTION: the steady route, with
+            otvm_trimap_apply_labels between the STM decoder's softmax and the encoding; with keyframe=True its slot is an anchor too.
+        The deferred memorize: the reference ends frame t with memorize(t) (alpha/model.py:461-493); here it opens frame t+1, so that
+        Encoder_M(t) and Encoder_Q(t+1), two chains of small launches that cannot fill 256 CUs on their own, run concurrently on two
+        HIP streams; they meet before the memory read.  The stages below are the frame's order of events (Frame step)."""
         keyframe = bool(keyframe)
-        if keyframe or labels is not None:
-            if B > 1 or train is not None:
-                raise NotImplementedError("otvm_amd: keyframe / labels apply to a single sequence (not to lock-step batches)")
-            if labels is not None and first_frame:
-                raise ValueError("otvm_amd: labels correct a propagated trimap; a first frame takes its trimap as tri_gt")
-            if keyframe and labels is None and tri_gt_l[0] is None:
-                raise ValueError("otvm_amd: keyframe=True needs the frame's trimap as tri_gt")
-            if max_memory_num < 2:
-                raise ValueError("otvm_amd: keyframe / labels need max_memory_num >= 2 (a bank of %d slot(s) holds no anchors)"
-                                 % max_memory_num)
-        kf_full = keyframe and labels is None and not first_frame   # a later frame that runs on its own trimap
-        no_segment = first_frame or kf_full
-        main = torch.cuda.current_stream(dev)
+        refuse_frame_args(a_l, fg_l, bg_l, tri_gt_l, first_frame, keyframe, labels, max_memory_num, train)
+        c = _FrameCall()
+        c.first_frame, c.train, c.main = first_frame, train, torch.cuda.current_stream(self.dev)
+        c.no_segment = first_frame or (keyframe and labels is None)   # a first frame, or a later one that runs on its own trimap
+        inputs_ready = self._stage_inputs(c, a_l, fg_l, bg_l, frames_rgb, labels, inputs_ready)
+        pend = self._open_frame(c, frame_id)
+        pl, c.pps = c.pl, self._preprocess_blocks(c)
+        use_side = self.prof is None and self.use_side_stream and not c.no_segment
+        ev_q, ev_s2, split = self._early_side_work(c, pend, inputs_ready) if use_side else (None, None, None)
+        self._memorize_and_preprocess(c, pend, use_side)
+        tri_srcs = self._trimap_sources(c, tri_gt_l, dilate_kernel)
+        self.last_T_read = 0
+        if c.no_segment:                                      # the frame's own trimap, padded, is the network's trimap input
+            for b in range(c.B):
+                L.check(self.lib.otvm_pad_trimap(tri_srcs[b].data_ptr(), c.H, c.W, pl.PROBS_B[b].data_ptr(), pl.Hp, pl.Wp, pl.lh, pl.lw,
+                                                 c.stream), "pad_trimap")
+        else:
+            self._segment_path(c, ev_q, ev_s2, split)
+        self._encode_and_alpha_network(c, cls_override)
+        if train is not None:
+            self._train_heads(c)
+        self._publish(c, last_frame, memorize, max_memory_num, first_frame or keyframe)
+        off_before = self.gn_predict_off
+        act = retry_decision(self.predict_check(pl, sync=first_frame), first_frame, _recheck, off_before, bool(pl._predicted))
+        if act == WARN_SUSPECT:
+            self._warn_suspect()
+        elif act != GO_ON:
+            if act == DROP_RECOMPUTE:
+                self._drop_plans()
+            # the whole call again, clip boundary included; what was published above is published again by the frame that is returned
+            return self._frame_batch(a_l, fg_l, bg_l, tri_gt_l, first_frame, last_frame, memorize, max_memory_num, dilate_kernel,
+                                     c.frame_id, cls_override, frames_rgb, None, train, _recheck=0 if off_before else _recheck - 1,
+                                     keyframe=keyframe, labels=labels)
+        if self.check_finite:
+            self._check_finite(c)
+        if last_frame or self.check_finite:
+            # end of the clip: the caller synchronises to collect its results -- the guard's verdict for the whole clip is
+            # read here (the reference's loop synchronises after every frame, eval.py:195-197)
+            self.guard_check(sync=True)
+        return [(o["scaled_imgs"], o["tri_out"], o["tri_gt_out"], o["alpha"], c.ins[b][0]) for b, o in enumerate(c.outs)]
+
+    def _record_ev_dec(self, main):                           # the query encoder's buffers are free from here on
+        self.ev_dec = _mark(main)
+
+    def _encode_and_alpha_network(self, c, cls_override):
+        """The trimap encoding and the alpha network.  ev_dec, which the NEXT frame's query encoder (side stream) waits for, is recorded
+        in front of the encoding on a frame without segment -- behind everything the launch stream was handed up to here: loop-invariant
+        inputs the caller created for this clip (the trimap flow's constant alpha) are complete -- and else, EVDEC_LATE, behind it: the
+        encoder's whole-CU kernels otherwise stall the encoding's three small ones, on the frame's serial chain (Frame step)."""
+        late = EVDEC_LATE and not c.no_segment
+        if not late:
+            self._record_ev_dec(c.main)
+        c.pl.encode(c.stream, cls_override)
+        if late:
+            self._record_ev_dec(c.main)
+        c.pl.run("fba", c.stream)
+        c.pl.run("fba_tail%d" % c.par, c.stream)
+        self.guard(c.pl.SMs[c.par].ch(0, 16), "hidden state", c.stream, c.frame_id)
+
+    def _stage_inputs(self, c, a_l, fg_l, bg_l, frames_rgb, labels, inputs_ready):
+        """Input staging: a / fg / bg of every image on the device in the form otvm_preprocess reads, one dtype and one resolution;
+        the label map.  Sets c.B, H, W, u8, rgb, ins, lab; returns ``inputs_ready`` as the side streams may use it."""
+        dev, f32, main = self.dev, torch.float32, c.main
         if isinstance(inputs_ready, torch.cuda.Event):
             main.wait_event(inputs_ready)                     # before anything below (a conversion, too) reads the inputs
         ins, H, W, converted = [], None, None, False
@@ -895,15 +1001,13 @@ class HipEngine:
                 raise ValueError("otvm_amd: the frames of a batch must share one dtype")
             if u8:
                 if bg.dtype != torch.uint8 or fg.dim() != 3 or fg.shape[-1] != 3 or bg.shape != fg.shape:
-                    raise ValueError("otvm_amd: uint8 frames must be [H,W,3] for both fg and bg, got %s / %s"
-                                     % (tuple(fg.shape), tuple(bg.shape)))
+                    raise ValueError("otvm_amd: uint8 frames must be [H,W,3] for both fg and bg, got %s / %s" % (tuple(fg.shape), tuple(bg.shape)))
                 fg, bg = fg.to(dev).contiguous(), bg.to(dev).contiguous()
                 h_, w_ = int(fg.shape[0]), int(fg.shape[1])
             else:
                 if frames_rgb:
                     raise ValueError("otvm_amd: frames_rgb applies to uint8 [H,W,3] frames only (fp32 input is BGR planar)")
-                fg = fg.to(dev, f32).contiguous()
-                bg = bg.to(dev, f32).contiguous()
+                fg, bg = fg.to(dev, f32).contiguous(), bg.to(dev, f32).contiguous()
                 h_, w_ = int(fg.shape[-2]), int(fg.shape[-1])
             if H is None:
                 H, W = h_, w_
@@ -911,299 +1015,223 @@ class HipEngine:
                 raise ValueError("otvm_amd: the sequences of a batch must share one resolution (%dx%d vs %dx%d)" % (w_, h_, W, H))
             converted = converted or a is not a_in or fg is not fg_in or bg is not bg_in
             if a.dim() != 5 or a.shape[0] != 1 or a.shape[1] != 1 or tuple(a.shape[-2:]) != (H, W):
-                raise ValueError("otvm_amd: inputs must be [1,1,C,H,W] (batch 1, one frame), got a %s for %dx%d frames"
-                                 % (tuple(a.shape), H, W))
+                raise ValueError("otvm_amd: inputs must be [1,1,C,H,W] (batch 1, one frame), got a %s for %dx%d frames" % (tuple(a.shape), H, W))
             ins.append((a, fg, bg))
-        if inputs_ready is not None and converted:
-            # an input was converted / copied just now BY THE LAUNCH STREAM (host tensor, other dtype, non-contiguous): the
-            # caller's promise covers the tensor it passed, not this copy -- the side streams must order themselves behind
-            # the launch stream (the conservative path), or the query encoder would read the copy before it is written
-            inputs_ready = None
-        if first_frame:
-            # the two forms are two plans (own buffers, launch lists and captured graphs; a switch re-keys, nothing is patched in
-            # place); tuned convolutions are shared through their layer signatures -- the refinement's last conv is tuned on the
-            # unfused route only, where it is the same launch in both forms
-            self._fgr_on = bool(self.foreground) and train is None
-        elif bool(self.foreground) != self._fgr_on and train is None:
-            raise RuntimeError("otvm_amd: `foreground` may only change at a clip's first frame")
-        lab = None
+        c.B, c.H, c.W, c.u8, c.rgb, c.ins, c.lab = len(ins), H, W, u8, u8 and frames_rgb, ins, None
         if labels is not None:
             lab = labels if torch.is_tensor(labels) else torch.as_tensor(labels)
             if lab.dtype != torch.uint8 or tuple(lab.shape) != (H, W):
                 raise ValueError("otvm_amd: labels must be a uint8 [%d,%d] map, got %s %s" % (H, W, lab.dtype, tuple(lab.shape)))
-            lab = lab.to(dev).contiguous()
-        pl = self.plan(H, W, B)
-        stream = self._stream()
-        outs = [dict(scaled_imgs=torch.empty((1, 1, 3, H, W), dtype=f32, device=dev),
-                     alpha=torch.empty((1, 1, 1, H, W), dtype=f32, device=dev),
-                     alpha_u8=torch.empty((H, W), dtype=torch.uint8, device=dev),
-                     tri_out=torch.empty((1, 1, 3, H, W), dtype=f32, device=dev),
-                     tri_gt_out=torch.empty((1, 1, 3, H, W), dtype=f32, device=dev)) for _ in range(B)]
-        # ---- deferred memorize of the previous frame (reference order: memorize(t) ends frame t, alpha/model.py:461-493;
-        # here it opens frame t+1 so that Encoder_M(t) and Encoder_Q(t+1), two chains of small launches that cannot fill
-        # 256 CUs on their own, run concurrently on two HIP streams; they meet before the memory read)
-        if first_frame:
+            c.lab = lab.to(dev).contiguous()
+        # an input was converted / copied just now BY THE LAUNCH STREAM (host tensor, other dtype, non-contiguous): the caller's
+        # promise covers the tensor it passed, not this copy -- the side streams must order themselves behind the launch stream
+        # (the conservative path), or the query encoder would read the copy before it is written
+        return None if converted else inputs_ready
+
+    def _open_frame(self, c, frame_id):
+        """Clip and frame bookkeeping: the plan (its form latched at a clip's first frame) and the output tensors, the clip boundary,
+        counters, the range guard's periodic look, parity.  Returns the previous frame's deferred memorize, still to be run."""
+        H, W, f32, u8 = c.H, c.W, dict(dtype=torch.float32, device=self.dev), dict(dtype=torch.uint8, device=self.dev)
+        if c.first_frame:
+            # the two forms are two plans (a switch re-keys, nothing is patched in place); tuned convolutions are shared through their
+            # layer signatures -- the refinement's last conv is tuned on the unfused route only, where both forms launch the same
+            self._fgr_on = bool(self.foreground) and c.train is None
+        elif bool(self.foreground) != self._fgr_on and c.train is None:
+            raise RuntimeError("otvm_amd: `foreground` may only change at a clip's first frame")
+        c.pl, c.stream = self.plan(H, W, c.B), self._stream()
+        c.outs = [dict(scaled_imgs=torch.empty((1, 1, 3, H, W), **f32), alpha=torch.empty((1, 1, 1, H, W), **f32),
+                       alpha_u8=torch.empty((H, W), **u8), tri_out=torch.empty((1, 1, 3, H, W), **f32),
+                       tri_gt_out=torch.empty((1, 1, 3, H, W), **f32)) for _ in range(c.B)]
+        if c.first_frame:
             if self.pending is not None:                      # previous clip ended without last_frame=True: its deferred
-                self.free_slots.append(self.pending["slot"])  # memorize is dropped, the slot goes back to the pool
+                self.free_slots.append(self.pending.slot)     # memorize is dropped, the slot goes back to the pool
             self.pending = None
             self.reset()
             self.frame_counter = 0
             self.gn_predict_suspect_from = None
-        if frame_id is None:                                  # position in the sequence since the last first_frame
-            frame_id = self.frame_counter
+        c.frame_id = self.frame_counter if frame_id is None else frame_id   # position in the sequence since the last first_frame
         self.frame_counter += 1
         self.guard_check(sync=False)
         pend, self.pending = self.pending, None
-        if pend is not None and pend["plan"] is not pl:
-            self._memorize(pend, stream)                      # resolution / batch changed: finish it in order
+        if pend is not None and pend.plan is not c.pl:
+            self._memorize(pend, c.stream)                    # resolution / batch changed: finish it in order
             pend = None
-        par = self.parity
-        self.parity ^= 1
-        pps = []
-        for (a, fg, bg) in ins:
-            pp = L.PreprocessParams()
-            pp.a = a.data_ptr()
-            if u8:
-                pp.fg_u8, pp.bg_u8, pp.u8_rgb = fg.data_ptr(), bg.data_ptr(), 1 if frames_rgb else 0
-            else:
-                pp.fg, pp.bg = fg.data_ptr(), bg.data_ptr()
-            pp.H, pp.W, pp.Hp, pp.Wp, pp.lh, pp.lw = H, W, pl.Hp, pl.Wp, pl.lh, pl.lw
+        c.par, self.parity = self.parity, self.parity ^ 1
+        return pend
+
+    def _preprocess_blocks(self, c):
+        """One otvm_preprocess parameter block per image: constants (a prototype made once), inputs, geometry; launches add outputs to a copy."""
+        if self._pp_proto is None:
+            self._pp_proto = L.PreprocessParams()
             for name, key in (("mean", "IMG_MEAN"), ("std", "IMG_STD"), ("mean_q", "trimap.model.Encoder_Q.mean"),
                               ("std_q", "trimap.model.Encoder_Q.std"), ("mean_m", "trimap.model.Encoder_M.mean"),
                               ("std_m", "trimap.model.Encoder_M.std")):
-                setattr(pp, name, (C.c_float * 3)(*self._consts(key)))
+                setattr(self._pp_proto, name, (C.c_float * 3)(*[float(x) for x in self.sd[key].flatten().tolist()]))
+        pl, pps = c.pl, []
+        for (a, fg, bg) in c.ins:
+            pp = L.PreprocessParams.from_buffer_copy(self._pp_proto)
+            pp.a = a.data_ptr()
+            if c.u8:
+                pp.fg_u8, pp.bg_u8, pp.u8_rgb = fg.data_ptr(), bg.data_ptr(), 1 if c.rgb else 0
+            else:
+                pp.fg, pp.bg = fg.data_ptr(), bg.data_ptr()
+            pp.H, pp.W, pp.Hp, pp.Wp, pp.lh, pp.lw = c.H, c.W, pl.Hp, pl.Wp, pl.lh, pl.lw
             pps.append(pp)
-        # ---- the query encoder (STM.segment's Encoder_Q + KV_Q) needs nothing but the frame itself.  It runs on a side
-        # stream: next to Encoder_M of the previous frame (two chains of small launches that cannot fill 256 CUs on their
-        # own), and -- when the caller vouches that the frame is already in device memory (inputs_ready) and the host runs
-        # ahead of the device -- already under the previous frame's alpha network, which is still executing on the launch
-        # stream.  Its buffers (SQ, the q_ trunk, QK, M4[512:]) were last read by the previous frame's STM decoder (ev_dec).
-        use_side = self.prof is None and self.use_side_stream and not no_segment
-        ev_q = ev_s2 = None
-        split = None                                          # memory read started on a side stream (see below)
-        if use_side:
-            if self.side is None:
-                self.side = torch.cuda.Stream(device=dev)
-            side = self.side
-            if self.ev_dec is not None:
-                side.wait_event(self.ev_dec)
-            if isinstance(inputs_ready, torch.cuda.Event):
-                side.wait_event(inputs_ready)                # (the launch stream waited at the top of the call)
-            elif inputs_ready is not True:                   # unknown producer: everything issued so far on the launch stream
-                ev_in = torch.cuda.Event()
-                ev_in.record(main)
-                side.wait_event(ev_in)
-            for b, (a, fg, bg) in enumerate(ins):
-                for t_ in (a, fg, bg):                       # read on the side stream too: keep the allocator from reusing them early
-                    t_.record_stream(side)
-                pq = L.PreprocessParams.from_buffer_copy(pps[b])
-                sq = pl.SQ.img(b)
-                pq.sq, pq.sq_ld = sq.ptr, sq.ld
-                L.check(lib.otvm_preprocess(C.byref(pq), side.cuda_stream), "preprocess (query encoder input)")
-            pl.run("segment_a", side.cuda_stream, side)
-            # The memory read is merged from per-chunk partials, so the bank may be visited in any grouping: every slot but
-            # the one the previous frame is about to memorise is resident already -- its partials are computed here, on
-            # the side stream, right behind the query key (i.e. also under the previous frame's alpha network); the launch
-            # stream later adds the one new slot and merges (1/T of the read stays on the critical path).
-            ev_q = torch.cuda.Event()
-            ev_q.record(side)
-            # ---- second side stream: the DENSE work of this frame that depends on the query encoder only -- the memory read
-            # over the slots that are already resident (the read is merged from per-chunk partials, so the bank may be
-            # visited in any grouping; only the slot the previous frame is about to memorise is missing) and the decoder's
-            # skip branches -- is held back until the previous frame's alpha network has finished (ev_m0) and then runs
-            # NEXT TO Encoder_M of the previous frame: that chain of small launches is on the critical path and cannot
-            # fill 256 CUs, these kernels can.  The launch stream then adds the one new slot, merges, and runs the rest of
-            # the decoder.
-            if self.side2 is None:
-                self.side2 = torch.cuda.Stream(device=dev)
-            side2 = self.side2
-            ev_m0 = torch.cuda.Event()
-            ev_m0.record(main)
-            side2.wait_event(ev_q)
-            side2.wait_event(ev_m0)
-            # the frame's own preprocess (composite, normalised copies for the alpha network and the next memorize) and the
-            # clearing of the GroupNorm statistics need neither encoder: off the launch stream's serial chain
-            if PRE_ON_S2:
-                for b, (a, fg, bg) in enumerate(ins):
-                    for t_ in (a, fg, bg):
-                        t_.record_stream(side2)
-                    outs[b]["scaled_imgs"].record_stream(side2)
-                pl.clear_stats(side2.cuda_stream)
-                for b in range(B):
-                    self._preprocess_rest(pl, pps[b], par, outs[b]["scaled_imgs"], False, side2.cuda_stream, b)
-            if self.precision == L.PREC_F16X3:
-                if pend is not None:
-                    nb, _ = bank_update(self.bank, pend["slot"], pend["first_frame"], pend["memorize"], pend["max_memory_num"],
-                                        pend["anchor"])
-                    old = [s_ for s_ in nb if s_ is not pend["slot"]]
-                    fresh = [pend["slot"]] if any(s_ is pend["slot"] for s_ in nb) else []
-                else:
-                    old, fresh = list(self.bank), []
-                if old:
-                    split = pl.memory_read_begin(old, fresh, side2.cuda_stream)
-            pl.run("segment_skip", side2.cuda_stream, side2)
-            ev_s2 = torch.cuda.Event()
-            ev_s2.record(side2)
-        # ---- deferred memorize of the previous frame (reference order: memorize(t) ends frame t, alpha/model.py:461-493;
-        # here it opens frame t+1 on the launch stream, concurrently with the query encoder above)
-        if pend is not None:
-            self._memorize(pend, stream)
-        if not (use_side and PRE_ON_S2):
-            pl.clear_stats(stream)
-            for b in range(B):
-                self._preprocess_rest(pl, pps[b], par, outs[b]["scaled_imgs"], not use_side, stream, b)
+        return pps
 
+    def _early_side_work(self, c, pend, inputs_ready):
+        """What this frame can do before the previous frame's memorize has run (the why: DESIGN.md, Frame step).  On ``side`` the query
+        encoder: it needs nothing but the frame itself -- with ``inputs_ready`` it starts under the previous frame's alpha network -- and
+        its buffers (SQ, the q_ trunk, QK, M4[512:]), last read by the previous frame's STM decoder (ev_dec).  On ``side2``, once that
+        alpha network is done (ev_m0), next to Encoder_M: statistics clear and preprocess (PRE_ON_S2), the read's partials over the
+        resident slots, the decoder's skip branches.  Returns what the launch stream joins later: ev_q, ev_s2, the split read."""
+        pl, ins, main = c.pl, c.ins, c.main
+        if self.side is None:
+            self.side, self.side2 = torch.cuda.Stream(device=self.dev), torch.cuda.Stream(device=self.dev)
+        side, side2 = self.side, self.side2
+        if self.ev_dec is not None:
+            side.wait_event(self.ev_dec)
+        if isinstance(inputs_ready, torch.cuda.Event):
+            side.wait_event(inputs_ready)                    # (the launch stream waited at the top of the call)
+        elif inputs_ready is not True:                       # unknown producer: everything issued so far on the launch stream
+            side.wait_event(_mark(main))
+        for b in range(c.B):
+            for t_ in ins[b]:                                # read on the side stream too: keep the allocator from reusing them early
+                t_.record_stream(side)
+            self._preprocess(c, b, side.cuda_stream, sq=True, rest=False)
+        pl.run("segment_a", side.cuda_stream, side)
+        ev_q, ev_m0 = _mark(side), _mark(main)
+        side2.wait_event(ev_q)
+        side2.wait_event(ev_m0)
+        if PRE_ON_S2:                                        # needs neither encoder: off the launch stream's serial chain
+            for b in range(c.B):
+                for t_ in ins[b] + (c.outs[b]["scaled_imgs"],):
+                    t_.record_stream(side2)
+            pl.clear_stats(side2.cuda_stream)
+            for b in range(c.B):
+                self._preprocess(c, b, side2.cuda_stream, sq=False)
+        old, fresh = early_read_split(self.bank, pend) if self.precision == L.PREC_F16X3 else ([], [])
+        split = pl.memory_read_begin(old, fresh, side2.cuda_stream) if old else None
+        pl.run("segment_skip", side2.cuda_stream, side2)
+        return ev_q, _mark(side2), split
+
+    def _memorize_and_preprocess(self, c, pend, use_side):
+        """On the launch stream, next to the query encoder: the deferred memorize, then what of the preprocess side2 did not take."""
+        if pend is not None:
+            self._memorize(pend, c.stream)
+        if not (use_side and PRE_ON_S2):
+            c.pl.clear_stats(c.stream)
+            for b in range(c.B):
+                self._preprocess(c, b, c.stream, sq=not use_side)
+
+    def _trimap_sources(self, c, tri_gt_l, dilate_kernel):
+        """Per image the trimap the caller sees as tri_gt (one-hot of the given one, or otvm_trimap_from_alpha) and its source."""
+        dev, f32, lib, H, W, stream = self.dev, torch.float32, self.lib, c.H, c.W, c.stream
         tri_srcs = []
-        for b in range(B):
-            tri_gt, tri_gt_out, a = tri_gt_l[b], outs[b]["tri_gt_out"], ins[b][0]
+        for b in range(c.B):
+            tri_gt, tri_gt_out, a = tri_gt_l[b], c.outs[b]["tri_gt_out"], c.ins[b][0]
             if tri_gt is not None:
                 tri_src = tri_gt.to(dev, f32).contiguous()
                 L.check(lib.otvm_onehot_argmax3(tri_src.data_ptr(), H * W, tri_gt_out.data_ptr(), stream), "onehot")
             else:
                 if dilate_kernel is None:
                     raise ValueError("otvm_amd: tri_gt=None needs a fixed dilate_kernel (reference eval always sets one)")
-                ws = pl.raws("tfa_ws", H * W, torch.uint8)[b]
+                ws = c.pl.raws("tfa_ws", H * W, torch.uint8)[b]
                 L.check(lib.otvm_trimap_from_alpha(a.data_ptr(), H, W, int(dilate_kernel), tri_gt_out.data_ptr(),
                                                    ws.data_ptr(), stream), "trimap_from_alpha")
                 tri_src = tri_gt_out
             tri_srcs.append(tri_src)
+        return tri_srcs
 
-        self.last_T_read = 0
-        if no_segment:
-            for b in range(B):
-                L.check(lib.otvm_pad_trimap(tri_srcs[b].data_ptr(), H, W, pl.PROBS_B[b].data_ptr(), pl.Hp, pl.Wp, pl.lh, pl.lw,
-                                            stream), "pad_trimap")
-            # frame 1's query encoder (side stream) is ordered behind everything the launch stream was handed up to here:
-            # loop-invariant inputs the caller created for this clip (the trimap flow's constant alpha) are complete
-            self.ev_dec = torch.cuda.Event()
-            self.ev_dec.record(main)
+    def _segment_path(self, c, ev_q, ev_s2, split):
+        """STM.segment on the launch stream: joins the side streams (or runs their lists), memory read, decoder, labels, training logits."""
+        lib, pl, main, stream, train, B = self.lib, c.pl, c.main, c.stream, c.train, c.B
+        if ev_q is not None:
+            main.wait_event(ev_q)
         else:
-            if ev_q is not None:
-                main.wait_event(ev_q)
-            else:
-                pl.run("segment_a", stream)
-                pl.run("segment_skip", stream)
-            if not self.bank:
-                raise RuntimeError("otvm_amd: non-first frame with an empty memory bank (call with first_frame=True first)")
-            self.last_T_read = len(self.bank)
-            if self.prof is not None:                         # bench.py roofline leg: HIP events around the memory read
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            if split is not None:
-                if len(split["old"]) + len(split["fresh"]) != len(self.bank) or not all(
-                        any(b_ is s_ for b_ in self.bank) for s_ in split["old"] + split["fresh"]):
-                    raise RuntimeError("otvm_amd: the early memory read visited a different bank than the policy produced")
-                pl.memory_read_fresh(split, stream)           # the slot just memorised: needs only the query key (ev_q)
-                main.wait_event(ev_s2)                        # partials of the resident slots + the decoder's skip branches
-                pl.memory_read_merge(split, stream)
-            else:
-                if ev_s2 is not None:
-                    main.wait_event(ev_s2)
-                pl.memory_read(self.bank, stream)
-            if self.prof is not None:
-                e1.record()
-                self.prof.append(("memory_read", 1280.0 * len(self.bank) * pl.hw * pl.hw * B, e0, e1, len(self.bank)))
-            pl.run("segment_b", stream)
-            self.guard(pl.L4, "propagated trimap logits", stream, frame_id)
-            if lab is not None:
-                L.check(lib.otvm_trimap_apply_labels(pl.PROBS_B[0].data_ptr(), lab.data_ptr(), H, W, pl.Hp, pl.Wp, pl.lh, pl.lw,
-                                                     stream), "trimap_apply_labels")
-            if train is not None and train.get("seg_logits") is not None:
-                for b in range(B):                             # the cross-entropy takes the logits (model.py:286-288)
-                    l4 = pl.L4.img(b)
-                    L.check(lib.otvm_upsample4_logits3(l4.ptr, l4.H, l4.W, l4.ld, train["seg_logits"][b].data_ptr(), stream),
-                            "upsample4_logits3")
-            if not EVDEC_LATE:
-                self.ev_dec = torch.cuda.Event()              # the query encoder's buffers are free again
-                self.ev_dec.record(main)
-        pl.encode(stream, cls_override)
-        if not no_segment and EVDEC_LATE:
-            # round 4: the NEXT frame's query encoder (side stream) is released behind the trimap encoding, not in front of
-            # it: its fused-bottleneck kernels (one workgroup per CU, every register of the CU) otherwise take the chip from
-            # the three small kernels of the encoding -- on the frame's serial chain -- which then wait for whole workgroups
-            # to drain (edt_rows_encode 204 us inside the frame against 90 us alone); the encoder still has the whole alpha
-            # network to hide under
-            self.ev_dec = torch.cuda.Event()
-            self.ev_dec.record(main)
-        pl.run("fba", stream)
-        pl.run("fba_tail%d" % par, stream)
-        self.guard(pl.SMs[par].ch(0, 16), "hidden state", stream, frame_id)
-        if train is not None:
-            # training forward (model.py:226-233,259-275): the fused (alpha, F, B) of both heads and the refinement's trimap
-            # logits feed the losses; frame 0 memorises the ground-truth trimap (preds_trimap_refine[0] = tri[:, 0])
-            sd, P_ = self.sd, pl.P
-            img = pl.D80.ch(67, 3)
-            for b in range(B):
-                hd, hr = pl.HID_D.img(b), pl.SMs[par].ch(0, 16).img(b)
-                L.check(lib.otvm_fba_head_train(hd.ptr, hd.ld, sd["NET.decoder.conv_up4.4.weight"].data_ptr(),
-                                                sd["NET.decoder.conv_up4.4.bias"].data_ptr(), 7, img.img(b).ptr, img.ld, P_,
-                                                train["dec7"][b].data_ptr(), 0, stream), "fba_head_train (decoder)")
-                L.check(lib.otvm_fba_head_train(hr.ptr, hr.ld, sd["NET.refine.pred.4.weight"].data_ptr(),
-                                                sd["NET.refine.pred.4.bias"].data_ptr(), 10, img.img(b).ptr, img.ld, P_,
-                                                train["ref7"][b].data_ptr(), train["ref_logits"][b].data_ptr(), stream),
-                        "fba_head_train (refinement)")
-                if train.get("tri0") is not None:
-                    smv = pl.SMs[par].ch(16, 8).img(b)
-                    L.check(lib.otvm_trimap_to_sm(train["tri0"][b].data_ptr(), P_, smv.ptr, smv.ld, stream), "trimap_to_sm")
+            pl.run("segment_a", stream)
+            pl.run("segment_skip", stream)
+        if not self.bank:
+            raise RuntimeError("otvm_amd: non-first frame with an empty memory bank (call with first_frame=True first)")
+        self.last_T_read = len(self.bank)
+        if self.prof is not None:                             # bench.py roofline leg: HIP events around the memory read
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        if split is not None:
+            if len(split.old) + len(split.fresh) != len(self.bank) or not all(
+                    any(b_ is s_ for b_ in self.bank) for s_ in split.old + split.fresh):
+                raise RuntimeError("otvm_amd: the early memory read visited a different bank than the policy produced")
+            pl.memory_read_fresh(split, stream)               # the slot just memorised: needs only the query key (ev_q)
+            main.wait_event(ev_s2)                            # partials of the resident slots + the decoder's skip branches
+            pl.memory_read_merge(split, stream)
+        else:
+            if ev_s2 is not None:
+                main.wait_event(ev_s2)
+            pl.memory_read(self.bank, stream)
+        if self.prof is not None:
+            e1.record()
+            self.prof.append(("memory_read", 1280.0 * len(self.bank) * pl.hw * pl.hw * B, e0, e1, len(self.bank)))
+        pl.run("segment_b", stream)
+        self.guard(pl.L4, "propagated trimap logits", stream, c.frame_id)
+        if c.lab is not None:
+            L.check(lib.otvm_trimap_apply_labels(pl.PROBS_B[0].data_ptr(), c.lab.data_ptr(), c.H, c.W, pl.Hp, pl.Wp, pl.lh, pl.lw,
+                                                 stream), "trimap_apply_labels")
+        if train is not None and train.get("seg_logits") is not None:
+            for b in range(B):                                 # the cross-entropy takes the logits (model.py:286-288)
+                l4 = pl.L4.img(b)
+                L.check(lib.otvm_upsample4_logits3(l4.ptr, l4.H, l4.W, l4.ld, train["seg_logits"][b].data_ptr(), stream), "upsample4_logits3")
+
+    def _train_heads(self, c):
+        """Training forward (model.py:226-233,259-275): the fused (alpha, F, B) of both heads and the refinement's trimap logits
+        feed the losses; frame 0 memorises the ground-truth trimap (preds_trimap_refine[0] = tri[:, 0])."""
+        lib, pl, par, train, stream, sd, P_ = self.lib, c.pl, c.par, c.train, c.stream, self.sd, c.pl.P
+        img = pl.D80.ch(67, 3)
+        for b in range(c.B):
+            for what, h, head, n, out, logits in (
+                    ("decoder", pl.HID_D.img(b), "NET.decoder.conv_up4.4", 7, train["dec7"][b].data_ptr(), 0),
+                    ("refinement", pl.SMs[par].ch(0, 16).img(b), "NET.refine.pred.4", 10, train["ref7"][b].data_ptr(),
+                     train["ref_logits"][b].data_ptr())):
+                L.check(lib.otvm_fba_head_train(h.ptr, h.ld, sd[head + ".weight"].data_ptr(), sd[head + ".bias"].data_ptr(), n,
+                                                img.img(b).ptr, img.ld, P_, out, logits, stream), "fba_head_train (%s)" % what)
+            if train.get("tri0") is not None:
+                smv = pl.SMs[par].ch(16, 8).img(b)
+                L.check(lib.otvm_trimap_to_sm(train["tri0"][b].data_ptr(), P_, smv.ptr, smv.ld, stream), "trimap_to_sm")
+
+    def _publish(self, c, last_frame, memorize, max_memory_num, anchor):
+        """The frame's results: the memorize it leaves for the next call (none behind a clip's last frame), the outputs, last_*."""
+        pl, outs = c.pl, c.outs
         if not last_frame:
             slot = pl.new_slot()
-            slot["frame"] = frame_id
-            self.pending = dict(plan=pl, par=par, slot=slot, first_frame=first_frame, memorize=memorize,
-                                max_memory_num=max_memory_num, anchor=first_frame or keyframe)
-        for b in range(B):
-            o = outs[b]
-            L.check(lib.otvm_crop_outputs(pl.ALPHA_P_B[b].data_ptr(), pl.TRI_P_B[b].data_ptr(), pl.Hp, pl.Wp, H, W, pl.lh, pl.lw,
-                                          o["alpha"].data_ptr(), o["alpha_u8"].data_ptr(), o["tri_out"].data_ptr(), stream), "crop")
+            slot["frame"] = c.frame_id
+            self.pending = Pending(slot, pl, c.par, c.first_frame, memorize, max_memory_num, anchor)
+        for o, alpha_p, tri_p in zip(outs, pl.ALPHA_P_B, pl.TRI_P_B):
+            L.check(self.lib.otvm_crop_outputs(alpha_p.data_ptr(), tri_p.data_ptr(), pl.Hp, pl.Wp, c.H, c.W, pl.lh, pl.lw,
+                                               o["alpha"].data_ptr(), o["alpha_u8"].data_ptr(), o["tri_out"].data_ptr(), c.stream), "crop")
         self.last_alpha_u8 = outs[0]["alpha_u8"]
         self.last_alpha_u8_b = [o["alpha_u8"] for o in outs]
-        # (a first frame computed twice -- the conditioning guard below -- comes through here twice: what is published belongs
-        # to the frame that is returned)
-        self._fgr_outputs(pl, outs, H, W, u8 and frames_rgb, stream)
+        self._fgr_outputs(pl, outs, c.H, c.W, c.rgb, c.stream)
         self.last_plan = pl
-        if pl._predicted and not self.gn_predict_off:
-            # conditioning guard of the predicted GroupNorm statistics (see GN_PREDICT_KAPPA_*): a clip's first frame is checked
-            # before it is returned (one synchronisation per clip) and computed again if a layer had to change its route -- the
-            # bank is empty there, so the frame call is repeatable; later frames are watched without synchronising
-            verdict = self.predict_check(pl, sync=first_frame)
-            if verdict == "off" and not first_frame:
-                # detected in the middle of a clip (asynchronous words, up to two check periods old): the plans are rebuilt at the
-                # next first_frame; the frames of THIS clip from `suspect` on were normalised with statistics now known to be
-                # ill-conditioned -- flagged for the caller (gn_predict_suspect_from, reset at the next first_frame), not hidden
-                import warnings
-                self.gn_predict_suspect_from = max(0, self.frame_counter - 1 - 16)
-                warnings.warn("otvm_amd: predicted GroupNorm statistics went ill-conditioned in the middle of a clip: its frames "
-                              "from %d on are suspect (engine.gn_predict_suspect_from); the rest of the clip keeps the current "
-                              "plan, the next clip runs on the accumulated route" % self.gn_predict_suspect_from)
-            if first_frame and verdict != "ok" and _recheck > 0:
-                if verdict == "off":
-                    self._drop_plans()                        # (rebuilt below without the predicted tails)
-                return self._frame_batch(a_l, fg_l, bg_l, tri_gt_l, first_frame, last_frame, memorize, max_memory_num, dilate_kernel,
-                                         frame_id, cls_override, frames_rgb, None, train, _recheck=_recheck - 1, keyframe=keyframe,
-                                         labels=labels)
-        elif self.gn_predict_off and pl._predicted and first_frame:
-            # the guard tripped in the middle of the previous clip: this clip's first frame ran on a plan that still predicts --
-            # rebuild now and compute it again
-            self._drop_plans()
-            return self._frame_batch(a_l, fg_l, bg_l, tri_gt_l, first_frame, last_frame, memorize, max_memory_num, dilate_kernel,
-                                     frame_id, cls_override, frames_rgb, None, train, _recheck=0, keyframe=keyframe,
-                                     labels=labels)
-        if self.check_finite and not all(bool(torch.isfinite(o["alpha"]).all()) for o in outs):
-            raise FloatingPointError("otvm_amd: non-finite alpha at frame %d -- an activation probably left fp16's range on the "
-                                     "f16x3 path; rerun with model.precision = 'f32' (exact-fp32 MFMA)" % frame_id)
-        if self.check_finite and pl.fgr and not all(bool(torch.isfinite(f).all()) for f in self.last_fgr_b):
-            raise FloatingPointError("otvm_amd: non-finite foreground at frame %d -- an activation probably left fp16's range on "
-                                     "the f16x3 path; rerun with model.precision = 'f32' (exact-fp32 MFMA)" % frame_id)
-        if last_frame or self.check_finite:
-            # end of the clip: the caller synchronises to collect its results -- the guard's verdict for the whole clip is
-            # read here (the reference's loop synchronises after every frame, eval.py:195-197)
-            self.guard_check(sync=True)
-        return [(o["scaled_imgs"], o["tri_out"], o["tri_gt_out"], o["alpha"], ins[b][0]) for b, o in enumerate(outs)]
+
+    def _warn_suspect(self):
+        """The conditioning guard said "off" in the middle of a clip (asynchronous words, up to two check periods old): the plans are
+        rebuilt at the next first_frame; the frames of THIS clip from `suspect` on were normalised with statistics now known to be
+        ill-conditioned -- flagged for the caller (gn_predict_suspect_from, reset at the next first_frame), not hidden."""
+        import warnings
+        self.gn_predict_suspect_from = max(0, self.frame_counter - 1 - 16)
+        warnings.warn("otvm_amd: predicted GroupNorm statistics went ill-conditioned in the middle of a clip: its frames "
+                      "from %d on are suspect (engine.gn_predict_suspect_from); the rest of the clip keeps the current "
+                      "plan, the next clip runs on the accumulated route" % self.gn_predict_suspect_from)
+
+    def _check_finite(self, c):
+        for what, tensors in (("alpha", [o["alpha"] for o in c.outs]), ("foreground", self.last_fgr_b if c.pl.fgr else [])):
+            if not all(bool(torch.isfinite(t).all()) for t in tensors):
+                raise FloatingPointError("otvm_amd: non-finite %s at frame %d -- an activation probably left fp16's range on the "
+                                         "f16x3 path; rerun with model.precision = 'f32' (exact-fp32 MFMA)" % (what, c.frame_id))
 
     def _fgr_outputs(self, pl, outs, H, W, rgb, stream):
         """otvm_fgr_outputs per image behind otvm_crop_outputs (same stream): F cropped, RGBA bytes, the composite."""
         if not pl.fgr:
-            self.last_fgr = self.last_rgba_u8 = self.last_comp_u8 = None
-            self.last_fgr_b = self.last_rgba_u8_b = self.last_comp_u8_b = None
+            self.last_fgr = self.last_rgba_u8 = self.last_comp_u8 = self.last_fgr_b = self.last_rgba_u8_b = self.last_comp_u8_b = None
             return
         dev, B = self.dev, len(outs)
         bgs = self.background if isinstance(self.background, list) else [self.background] * B
@@ -1234,39 +1262,30 @@ class HipEngine:
         self.last_fgr, self.last_rgba_u8, self.last_comp_u8 = fl[0], rl[0], cl[0]
         self.last_fgr_b, self.last_rgba_u8_b, self.last_comp_u8_b = fl, rl, cl
 
-    def _preprocess_rest(self, pl, pp, par, scaled_imgs, with_sq, stream, b=0):
-        """otvm_preprocess of image ``b`` for everything but (with_sq False) the query encoder's input: the composite returned
-        to the caller, the alpha network's input channels, the next memorize's image channels, the refinement's image channels."""
-        pm = L.PreprocessParams.from_buffer_copy(pp)
-        pm.scaled_imgs = scaled_imgs.data_ptr()
-        x11 = pl.X11.img(b)
-        pm.x11, pm.x11_ld = x11.ptr, x11.ld
-        if with_sq:
-            sq = pl.SQ.img(b)
-            pm.sq, pm.sq_ld = sq.ptr, sq.ld
-        smv = pl.SMs[par].ch(16, 8).img(b)
-        pm.sm, pm.sm_ld = smv.ptr, smv.ld
-        d80 = pl.D80.img(b)
-        pm.d80, pm.d80_ld = d80.ptr, d80.ld
-        L.check(self.lib.otvm_preprocess(C.byref(pm), stream), "preprocess")
+    def _preprocess(self, c, b, stream, sq, rest=True):
+        """otvm_preprocess of image ``b``: the query encoder's input (``sq``) and / or the ``rest`` -- the composite returned to the
+        caller, the alpha network's input channels, the next memorize's image channels, the refinement's image channels."""
+        pm, pl = L.PreprocessParams.from_buffer_copy(c.pps[b]), c.pl
+        if sq:
+            v = pl.SQ.img(b)
+            pm.sq, pm.sq_ld = v.ptr, v.ld
+        if rest:
+            pm.scaled_imgs = c.outs[b]["scaled_imgs"].data_ptr()
+            x11, smv, d80 = pl.X11.img(b), pl.SMs[c.par].ch(16, 8).img(b), pl.D80.img(b)
+            pm.x11, pm.x11_ld, pm.sm, pm.sm_ld, pm.d80, pm.d80_ld = x11.ptr, x11.ld, smv.ptr, smv.ld, d80.ptr, d80.ld
+        L.check(self.lib.otvm_preprocess(C.byref(pm), stream), "preprocess" if rest else "preprocess (query encoder input)")
 
     def _memorize(self, pend, stream, tstream=None):
         """STM.memorize of a finished frame + the bank policy (alpha/model.py:466-493), on ``stream``."""
-        pl, slot = pend["plan"], pend["slot"]
-        pl.run("mem_stem%d" % pend["par"], stream, tstream)
+        pl = pend.plan
+        pl.run("mem_stem%d" % pend.par, stream, tstream)
         pl.run("mem_trunk", stream, tstream)
-        pl.kv_into_slot(slot, stream)
-        self.bank, released = bank_update(self.bank, slot, pend["first_frame"], pend["memorize"], pend["max_memory_num"],
-                                          pend["anchor"])
+        pl.kv_into_slot(pend.slot, stream)
+        self.bank, released = pend.apply(self.bank)
         self.free_slots.extend(released)
 
     def _bank_with_pending(self):
-        bank = list(self.bank)
-        pend = self.pending
-        if pend is not None:
-            bank, _ = bank_update(bank, pend["slot"], pend["first_frame"], pend["memorize"], pend["max_memory_num"],
-                                  pend["anchor"])
-        return bank
+        return list(self.bank) if self.pending is None else self.pending.apply(list(self.bank))[0]
 
     def bank_frames(self):
         """Frame ids resident in the bank, including a memorize that is still deferred (host-side policy only)."""
@@ -1280,11 +1299,10 @@ class HipEngine:
         """Leave only the anchor slots in the bank (a sweep in the other direction starts from the keyframes alone).  A deferred
         memorize of an anchor is carried out first; one of any other frame is dropped with its slot, unmemorised."""
         pend = self.pending
-        if pend is not None and (pend["anchor"] or pend["first_frame"]):
-            self.flush()
-        elif pend is not None:
+        if pend is not None and not (pend.anchor or pend.first_frame):
             self.pending = None
-            self.free_slots.append(pend["slot"])
+            self.free_slots.append(pend.slot)
+        self.flush()
         self.free_slots.extend(s for s in self.bank if not _is_anchor(s))
         self.bank = [s for s in self.bank if _is_anchor(s)]
 
@@ -1295,14 +1313,6 @@ class HipEngine:
             with torch.cuda.device(self.dev):
                 self._memorize(pend, self._stream())
                 self.guard_check(sync=True)
-
-    def _consts(self, key):
-        c = getattr(self, "_const_cache", None)
-        if c is None:
-            c = self._const_cache = {}
-        if key not in c:
-            c[key] = self._vec3(key)
-        return c[key]
 
 
 class FramePlan:
@@ -2103,7 +2113,7 @@ class FramePlan:
         S = []
         self.r4m, _, _ = self.stm_trunk(S, stem, m_, "m_")
         self.steps["mem_trunk"] = S
-        self.mem_ws = None
+        self.mem_ws = [None] * self.B                         # the memory read's workspace per image (_mem_ws_for)
 
     # ------------------------------------------------------------------ run
     def run(self, key, stream, tstream=None):
@@ -2159,8 +2169,6 @@ class FramePlan:
     # ---- memory read (STM.py:140-163).  Every image of a batch has its own bank (per-sequence slots) and its own
     # workspace: the read is launched per image (three launches of ~320 per frame; the rest of the frame is batched)
     def _mem_ws_for(self, b, need):
-        if self.mem_ws is None:
-            self.mem_ws = [None] * self.B
         w = self.mem_ws[b]
         if w is None or w.numel() < need:
             torch.cuda.synchronize(self.dev)                  # (rare: the bank grew; nothing in flight may use the old one)
@@ -2186,41 +2194,30 @@ class FramePlan:
     def memory_read_begin(self, old, fresh, stream):
         """f16x3 memory read, first step: partials over the slots ``old`` (already resident) on ``stream``; ``fresh`` (the
         slot being memorised right now, 0 or 1 entries) follows in memory_read_fresh."""
-        lib = self.lib
-        np_cap = int(lib.otvm_memory_read_f16x3_partial_count(len(old), self.hw))
-        if fresh:
-            np_cap += int(lib.otvm_memory_read_f16x3_partial_count(len(fresh), self.hw))
-        need = np_cap * self.hw * (512 + 2) * 4
-        wss, done = [], 0
-        for b in range(self.B):
-            ws = self._mem_ws_for(b, need)
-            qk = self.QK.img(b)
-            arr = (C.c_void_p * len(old))(*[s["packed_b"][b].data_ptr() for s in old])
-            end = C.c_int(0)
-            L.check(lib.otvm_memory_read_f16x3_partial(qk.ptr, qk.ld, arr, len(old), self.hw, ws.data_ptr(), np_cap, 0, C.byref(end),
-                                                       stream), "memory_read_f16x3_partial")
-            wss.append(ws)
-            done = end.value
-        return dict(old=old, fresh=fresh, np_cap=np_cap, done=done, ws=wss)
+        np_cap = sum(int(self.lib.otvm_memory_read_f16x3_partial_count(len(s), self.hw)) for s in (old, fresh) if s)
+        ws = [self._mem_ws_for(b, np_cap * self.hw * (512 + 2) * 4) for b in range(self.B)]
+        return self._read_partials(SplitRead(old, fresh, np_cap, 0, ws), old, stream)
 
     def memory_read_fresh(self, split, stream):
-        lib, n = self.lib, split["done"]
-        if split["fresh"]:
-            fr = split["fresh"]
-            for b in range(self.B):
-                qk = self.QK.img(b)
-                arr = (C.c_void_p * len(fr))(*[s["packed_b"][b].data_ptr() for s in fr])
-                end = C.c_int(0)
-                L.check(lib.otvm_memory_read_f16x3_partial(qk.ptr, qk.ld, arr, len(fr), self.hw, split["ws"][b].data_ptr(),
-                                                           split["np_cap"], n, C.byref(end), stream), "memory_read_f16x3_partial")
-            n = end.value
-        split["done"] = n
+        return self._read_partials(split, split.fresh, stream) if split.fresh else split
+
+    def _read_partials(self, split, slots, stream):
+        """Partials over ``slots`` of every image, appended behind the ``split.done`` partials its workspace holds already."""
+        end = C.c_int(0)
+        for b in range(self.B):
+            qk = self.QK.img(b)
+            arr = (C.c_void_p * len(slots))(*[s["packed_b"][b].data_ptr() for s in slots])
+            L.check(self.lib.otvm_memory_read_f16x3_partial(qk.ptr, qk.ld, arr, len(slots), self.hw, split.ws[b].data_ptr(),
+                                                            split.np_cap, split.done, C.byref(end), stream), "memory_read_f16x3_partial")
+        split.done = end.value
+        return split
 
     def memory_read_merge(self, split, stream):
         for b in range(self.B):
             out = self.M4.ch(0, 512).img(b)
-            L.check(self.lib.otvm_memory_read_f16x3_combine(split["ws"][b].data_ptr(), split["np_cap"], split["done"], self.hw,
+            L.check(self.lib.otvm_memory_read_f16x3_combine(split.ws[b].data_ptr(), split.np_cap, split.done, self.hw,
                                                             out.ptr, out.ld, stream), "memory_read_f16x3_combine")
+        return split
 
     def kv_into_slot(self, slot, stream):
         if "kv_steps" not in slot:
