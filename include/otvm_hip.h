@@ -79,7 +79,9 @@ const char* otvm_last_error(void);
                                   otvm_roi_track_params, and otvm_roi_crop_at / otvm_roi_paste_at, which take the two structs above
                                   as they are plus a device pointer;
                                   likewise multi-subject matting: otvm_subjects_track, otvm_subjects_crop, otvm_subjects_bbox and
-                                  otvm_subjects_resolve with their otvm_subjects_*_params) */
+                                  otvm_subjects_resolve with their otvm_subjects_*_params;
+                                  likewise video streams: otvm_yuv_to_rgb and otvm_rgb_to_yuv420 with otvm_yuv_to_rgb_params and
+                                  otvm_rgb_to_yuv420_params) */
 int otvm_abi_version(void);
 
 /* ---------------------------------------------------------------- weights (load time) ----------
@@ -850,6 +852,80 @@ typedef struct otvm_subjects_resolve_params {
     uint8_t* owner;                                  /* [H,W] */
 } otvm_subjects_resolve_params;
 int otvm_subjects_resolve(const otvm_subjects_resolve_params* p, void* stream);
+
+/* ---------------------------------------------------------------- video streams: YUV <-> RGB ----------
+ * 8-bit YUV as a decoder or a Y4M stream holds it <-> the uint8 [H,W,3] frames the rest of this interface takes (an extension;
+ * otvm_amd/yuv.py, python -m otvm_amd.y4m_cli).  Integer arithmetic throughout, no atomics: two calls give equal bits, and
+ * tests/yuv_ref.py restates both kernels operation by operation.  Checked by definition only (bilinear chroma at the stated
+ * siting, the matrix of the stated standard, round half up, clamp): within one code value of the float64 definition.  Both run on
+ * the caller's stream, never synchronise with the host, and launch nothing when an argument is refused (nonzero;
+ * otvm_last_error() starts with the function's name).  Sides are 1 .. 65535; every offset is formed in 64 bits.  Every plane has
+ * its own pointer and its own row stride in bytes (>= the row's bytes), so a frame buffer is addressed where it lies.  New symbols
+ * only (additive, as the entries above): the ABI number stays.
+ *
+ * Chroma sizes: cw = (W + 1) / 2, ch = (H + 1) / 2.  Layouts: 420P has u, v [ch,cw]; NV12 has one plane [ch,cw,2] = (U, V) given
+ * as u (v is not looked at); 422P has u, v [H,cw]; 444P has u, v [H,W]; MONO has no chroma (U = V = 128; u, v not looked at).
+ *
+ * otvm_yuv_to_rgb.  Chroma at luma resolution is bilinear, weights in quarters per axis, indices clamped to the plane:
+ *   horizontal, c = x >> 1 (420P, NV12, 422P):
+ *     OTVM_YUV_SITING_CENTRE  even x: 3 C[c] + C[c-1],  odd x: 3 C[c] + C[c+1]
+ *     OTVM_YUV_SITING_LEFT    even x: 4 C[c],           odd x: 2 C[c] + 2 C[c+1]
+ *     444P: 4 C[x] (siting is not looked at beyond being a known value)
+ *   vertical, r = y >> 1 (420P, NV12: always centre): even y: 3 row[r] + row[r-1], odd y: 3 row[r] + row[r+1]; otherwise 4 row[y].
+ *   The product of the two is the integer u16 = 16 x chroma, NOT rounded; du = u16 - 2048, dv likewise.
+ * Matrix, 20 fractional bits, one rounding, arithmetic shift, clamp to 0 .. 255, with yo = 16 (limited) or 0 (full):
+ *     R = (CY (Y - yo) + RV dv           + 2^19) >> 20
+ *     G = (CY (Y - yo) - GU du - GV dv   + 2^19) >> 20
+ *     B = (CY (Y - yo) + BU du           + 2^19) >> 20
+ *   (CY, RV, GU, GV, BU), the chroma ones carrying the 1/16:  BT.601 limited 1220945, 104597, 25675, 53279, 132201;
+ *   BT.601 full 1048576, 91881, 22553, 46802, 116130;  BT.709 limited 1220945, 117489, 13975, 34925, 138438;
+ *   BT.709 full 1048576, 103206, 12276, 30679, 121609.  Full range: CY = 2^20, so (v, 128, 128) gives R = G = B = v exactly.
+ * rgb is [H,W,3] contiguous, stored R, G, B when u8_rgb != 0 and B, G, R otherwise.
+ *
+ * otvm_rgb_to_yuv420: img uint8 [H,W,3] (u8_rgb as above) -> planar y [H,W], u, v [ch,cw], chroma sited at the centre of its
+ * 2 x 2 block ("C420jpeg").  With yo as above and co = 128:
+ *     Y = ((YR R + YG G + YB B + 2^19) >> 20) + yo
+ *     U = ((-UR sR - UG sG + CH sB + (co << 22) + 2^21) >> 22),  V = ((CH sR - VG sG - VB sB + (co << 22) + 2^21) >> 22), clamped
+ *   where sR, sG, sB are the SUMS over the block's four pixels, coordinates clamped to the image (an odd edge counts the edge
+ *   pixel twice): one integer expression, one rounding, no intermediate mean.  UG = CH - UR and VG = CH - VB, so the chroma rows
+ *   sum to zero, and YR + YG + YB is the range's scale exactly (2^20 in full range): grey v gives (v, 128, 128) in full range.
+ *   (YR, YG, YB, CH, UR, VB):  BT.601 limited 269262, 528618, 102662, 460551, 155423, 74897;
+ *   BT.601 full 313524, 615514, 119538, 524288, 176932, 85262;  BT.709 limited 191455, 644068, 65019, 460551, 105533, 42230;
+ *   BT.709 full 222927, 749942, 75707, 524288, 120138, 48074.                                                                   */
+#define OTVM_YUV_420P 0
+#define OTVM_YUV_NV12 1
+#define OTVM_YUV_422P 2
+#define OTVM_YUV_444P 3
+#define OTVM_YUV_MONO 4
+#define OTVM_YUV_BT601 0
+#define OTVM_YUV_BT709 1
+#define OTVM_YUV_LIMITED 0
+#define OTVM_YUV_FULL 1
+#define OTVM_YUV_SITING_LEFT 0
+#define OTVM_YUV_SITING_CENTRE 1
+typedef struct otvm_yuv_to_rgb_params {
+    int H, W;
+    int layout, matrix, range, siting;      /* OTVM_YUV_* */
+    int y_stride, u_stride, v_stride;       /* bytes per row of each plane */
+    int u8_rgb;
+    const uint8_t* y;
+    const uint8_t* u;                       /* NV12: the interleaved plane */
+    const uint8_t* v;
+    uint8_t* rgb;                           /* [H,W,3] */
+} otvm_yuv_to_rgb_params;
+int otvm_yuv_to_rgb(const otvm_yuv_to_rgb_params* p, void* stream);
+
+typedef struct otvm_rgb_to_yuv420_params {
+    int H, W;
+    int matrix, range;                      /* OTVM_YUV_* */
+    int y_stride, u_stride, v_stride;       /* bytes per row of each plane */
+    int u8_rgb;
+    const uint8_t* img;                     /* [H,W,3] */
+    uint8_t* y;                             /* [H,W] */
+    uint8_t* u;                             /* [ch,cw] */
+    uint8_t* v;                             /* [ch,cw] */
+} otvm_rgb_to_yuv420_params;
+int otvm_rgb_to_yuv420(const otvm_rgb_to_yuv420_params* p, void* stream);
 
 /* ---------------------------------------------------------------- range guard / clear -----------
  * f16x3 splits fp32 operands into fp16 halves: |x| >= 65504 loses accuracy, >= 131008 becomes inf.

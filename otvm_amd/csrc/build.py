@@ -35,6 +35,7 @@ SOURCES = [
     ("temporal.hip", ["-ffp-contract=off"]),
     ("roi.hip", ["-ffp-contract=off"]),
     ("subjects.hip", ["-ffp-contract=off"]),
+    ("yuv.hip", []),
     ("memory_read.hip", []),
     ("memory_read_f16x3.hip", []),
     ("metrics.hip", []),

@@ -147,6 +147,23 @@ class SubjectsResolveParams(C.Structure):
                 ("union_alpha", vp), ("union_u8", vp), ("owner", vp)]
 
 
+class YuvToRgbParams(C.Structure):
+    """otvm_yuv_to_rgb_params (additive to ABI 21); the YUV_* numbers below are the header's OTVM_YUV_*."""
+    _fields_ = [("H", i32), ("W", i32), ("layout", i32), ("matrix", i32), ("range", i32), ("siting", i32),
+                ("y_stride", i32), ("u_stride", i32), ("v_stride", i32), ("u8_rgb", i32), ("y", vp), ("u", vp), ("v", vp), ("rgb", vp)]
+
+
+class RgbToYuv420Params(C.Structure):
+    _fields_ = [("H", i32), ("W", i32), ("matrix", i32), ("range", i32), ("y_stride", i32), ("u_stride", i32), ("v_stride", i32),
+                ("u8_rgb", i32), ("img", vp), ("y", vp), ("u", vp), ("v", vp)]
+
+
+YUV_420P, YUV_NV12, YUV_422P, YUV_444P, YUV_MONO = 0, 1, 2, 3, 4
+YUV_BT601, YUV_BT709 = 0, 1
+YUV_LIMITED, YUV_FULL = 0, 1
+YUV_SITING_LEFT, YUV_SITING_CENTRE = 0, 1
+
+
 class PpmHeadParams(C.Structure):
     _fields_ = [("pooled", vp), ("C", i32), ("K_pad", i32), ("Cout", i32),
                 ("w", vp * 4), ("bias", vp * 4), ("gamma", vp * 4), ("beta", vp * 4), ("out", vp * 4),
@@ -234,6 +251,8 @@ _PROTOS = {
     "otvm_subjects_crop": (i32, [C.POINTER(SubjectsCropParams), vp]),
     "otvm_subjects_bbox": (i32, [C.POINTER(SubjectsBboxParams), vp]),
     "otvm_subjects_resolve": (i32, [C.POINTER(SubjectsResolveParams), vp]),
+    "otvm_yuv_to_rgb": (i32, [C.POINTER(YuvToRgbParams), vp]),
+    "otvm_rgb_to_yuv420": (i32, [C.POINTER(RgbToYuv420Params), vp]),
     "otvm_gn_stats_b": (i32, [vp, i64, i32, i32, vp, i32, i64, i32, vp]),
     "otvm_gn_table_b": (i32, [vp, i64, i32, vp, vp, vp, vp, i32, i32, i32, vp]),
     "otvm_gn_apply_b": (i32, [C.POINTER(GnApplyParams), vp]),
