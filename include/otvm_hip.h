@@ -81,7 +81,9 @@ const char* otvm_last_error(void);
                                   likewise multi-subject matting: otvm_subjects_track, otvm_subjects_crop, otvm_subjects_bbox and
                                   otvm_subjects_resolve with their otvm_subjects_*_params;
                                   likewise video streams: otvm_yuv_to_rgb and otvm_rgb_to_yuv420 with otvm_yuv_to_rgb_params and
-                                  otvm_rgb_to_yuv420_params) */
+                                  otvm_rgb_to_yuv420_params;
+                                  likewise masks of keyed footage: otvm_mask_from_chroma and otvm_mask_from_plate with
+                                  otvm_mask_from_chroma_params and otvm_mask_from_plate_params) */
 int otvm_abi_version(void);
 
 /* ---------------------------------------------------------------- weights (load time) ----------
@@ -926,6 +928,51 @@ typedef struct otvm_rgb_to_yuv420_params {
     uint8_t* v;                             /* [ch,cw] */
 } otvm_rgb_to_yuv420_params;
 int otvm_rgb_to_yuv420(const otvm_rgb_to_yuv420_params* p, void* stream);
+
+/* ---------------------------------------------------------------- masks of keyed footage --------
+ * The mask otvm_trimap_from_mask takes, made from the frame itself: frame uint8 [H,W,3] -> mask uint8 [H,W], 255 = subject,
+ * 0 = screen / plate, every element written.  Integer arithmetic throughout, no atomics: two calls give equal bits.  Both run on
+ * the caller's stream, never synchronise with the host, and launch nothing when an argument is refused (nonzero;
+ * otvm_last_error() starts with the function's name).  Sides are 1 .. 16383; every offset is formed in 64 bits.  Any base
+ * address and any W is taken (four pixels move as dwords when W % 4 == 0 and frame and mask are 4-byte aligned, byte by byte
+ * otherwise).  New symbols only (additive, as the entries above): the ABI number stays.
+ *
+ * otvm_mask_from_chroma: a hue-cone key that does not depend on brightness.  u8_rgb says which byte is R, as
+ * otvm_preprocess_params.u8_rgb does.  Per pixel, with the chroma rows of otvm_rgb_to_yuv420's BT.601 full-range matrix
+ * (CH, UR, VB) = (524288, 176932, 85262), UG = CH - UR, VG = CH - VB, applied to ONE pixel with 20 fractional bits:
+ *     Cb = clamp((-UR R - UG G + CH B + (128 << 20) + 2^19) >> 20, 0, 255),  cb = Cb - 128
+ *     Cr = clamp(( CH R - VG G - VB B + (128 << 20) + 2^19) >> 20, 0, 255),  cr = Cr - 128
+ *     q  = (cb kb + cr kr) - |cb kr - cr kb|
+ *   (kb, kr) are cb, cr of the key colour, computed by the caller by the same rule: -128 .. 127, refused when
+ *   kb^2 + kr^2 < 16^2 (a grey key has no hue).  q is positive inside the 45 degree cone round the key's hue and grows with
+ *   saturation.  With -2^20 <= qlo < qhi <= 2^20 (the caller's chroma thresholds times |K| = sqrt(kb^2 + kr^2), rounded):
+ *     mask = 255 where q <= qlo, 0 where q >= qhi, 255 - ((q - qlo) 255) / (qhi - qlo) between them (floor division).
+ *
+ * otvm_mask_from_plate: a difference key against a clean plate, plate uint8 [H,W,3] in the frame's channel order (the
+ * distance is symmetric in the channels, so the order itself is not asked for).  For pixel x and radius r in 0 .. 3
+ *     d(x) = min over the plate pixels x' of the (2r+1)^2 neighbourhood of x, coordinates clamped to the image,
+ *            of max_c |I_c(x) - P_c(x')|
+ *   and with 0 <= lo < hi <= 255:
+ *     mask = 0 where d <= lo, 255 where d >= hi, ((d - lo) 255) / (hi - lo) between them (floor division).               */
+typedef struct otvm_mask_from_chroma_params {
+    const uint8_t* frame;                   /* [H,W,3] */
+    uint8_t* mask;                          /* [H,W] */
+    int H, W;
+    int u8_rgb;
+    int kb, kr;                             /* the key colour's cb, cr */
+    int qlo, qhi;
+} otvm_mask_from_chroma_params;
+int otvm_mask_from_chroma(const otvm_mask_from_chroma_params* p, void* stream);
+
+typedef struct otvm_mask_from_plate_params {
+    const uint8_t* frame;                   /* [H,W,3] */
+    const uint8_t* plate;                   /* [H,W,3] */
+    uint8_t* mask;                          /* [H,W] */
+    int H, W;
+    int radius;                             /* 0 .. 3 */
+    int lo, hi;
+} otvm_mask_from_plate_params;
+int otvm_mask_from_plate(const otvm_mask_from_plate_params* p, void* stream);
 
 /* ---------------------------------------------------------------- range guard / clear -----------
  * f16x3 splits fp32 operands into fp16 halves: |x| >= 65504 loses accuracy, >= 131008 becomes inf.

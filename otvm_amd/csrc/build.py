@@ -36,6 +36,7 @@ SOURCES = [
     ("roi.hip", ["-ffp-contract=off"]),
     ("subjects.hip", ["-ffp-contract=off"]),
     ("yuv.hip", []),
+    ("key_mask.hip", []),
     ("memory_read.hip", []),
     ("memory_read_f16x3.hip", []),
     ("metrics.hip", []),

@@ -60,6 +60,14 @@ size, and the windows run as one lock-step batch; without --roi the subjects run
 Checked by definition only.  Refused without --demo, with --roi auto or a static window, --keyframes, --masks, --work-scale,
 --stabilise, --viz, --composite and --batch > 1.  The summary carries subjects and subjects_overlap; between clips whose window
 size or number of subjects differs the engine's frame plans are dropped.
+--key green|blue|R,G,B [--key-thresholds LO,HI] | --plate PATH [--plate-thresholds LO,HI] [--plate-radius R] (demo layout):
+trimap-free matting of keyed footage (video.run_video_matte(key=...), otvm_amd/keys.py).  No trimap/ or mask/ folder is read: every
+frame's mask is made on the device from the frame itself -- a hue-cone chroma key round the screen's colour, or the difference to a
+clean plate of the empty set (an image of the frames' resolution) -- made into a trimap as a mask is (--mask-band and
+--mask-thresholds apply), and the frame is matted from it alone; nothing is propagated.  Every default is a PLACEHOLDER, the keys
+are checked by definition only, and nothing is claimed about quality on real footage.  Works with --fgr, --composite, --work-scale,
+--stabilise and --roi auto|Y0,X0,H,W; --key and --plate exclude each other, --masks, --keyframes, --subjects, --roi track and
+--batch > 1, and are refused without --demo.  The summary carries key.
 Frame IO runs through otvm_amd/io_pipeline.py: the demo flow decodes ahead in a thread pool and uploads on a copy
 stream, both flows download the 8-bit alphas asynchronously and PNG-encode them in a pool (the reference's loop blocks
 on .cpu() + cv2.imwrite per frame, eval.py:209-217).
@@ -156,6 +164,81 @@ def parse_roi_options(roi, margin):
     return roi, 32 if margin is None else margin
 
 
+def add_key_arguments(ap):
+    """--key / --plate and their options, for every command line that takes them (parse_key_options reads them back)"""
+    ap.add_argument("--key", default=None, metavar="green|blue|R,G,B",
+                    help="trimap-free matting of footage shot against a screen: every frame's mask is keyed on the device from "
+                         "the frame itself (a hue-cone chroma key), then made into a trimap as a mask is")
+    ap.add_argument("--key-thresholds", default=None, metavar="LO,HI",
+                    help="--key: subject up to LO, screen from HI, in chroma code values (default 8,24: placeholders, not tuned on "
+                         "real footage)")
+    ap.add_argument("--plate", default=None, metavar="PATH",
+                    help="trimap-free matting of a locked-off shot: every frame's mask is its difference to this clean plate of the "
+                         "empty set (an image of the frames' resolution)")
+    ap.add_argument("--plate-thresholds", default=None, metavar="LO,HI",
+                    help="--plate: plate up to LO, subject from HI, 0 <= LO < HI <= 255 (default 12,40: placeholders)")
+    ap.add_argument("--plate-radius", type=int, default=None, metavar="R",
+                    help="--plate: the plate is searched in a (2R+1)^2 neighbourhood, R in 0 ... 3 (default 1: a placeholder)")
+
+
+def parse_key_options(args, who="eval_cli"):
+    """--key green|blue|R,G,B [--key-thresholds LO,HI] | --plate PATH [--plate-thresholds LO,HI] [--plate-radius R] -> None, or
+    make(band, mask_lo, mask_hi, H, W, rgb) -> run_video_matte's ``key`` (the plate is read, once, when the frames' size and channel
+    order are known).  Everything that needs no image is checked here, as keys.ChromaKey / keys.PlateKey do."""
+    from . import keys
+    if args.key is not None and args.plate is not None:
+        raise SystemExit("%s: --key and --plate exclude each other (one key makes the mask)" % who)
+    if args.key is None and args.key_thresholds is not None:
+        raise SystemExit("%s: --key-thresholds belongs to --key" % who)
+    if args.plate is None and (args.plate_thresholds is not None or args.plate_radius is not None):
+        raise SystemExit("%s: --plate-thresholds / --plate-radius belong to --plate" % who)
+    if args.key is None and args.plate is None:
+        return None
+    if args.key is not None:
+        colour = args.key
+        if colour not in keys.COLOURS:
+            parts = colour.split(",")
+            if len(parts) != 3 or not all(x.strip().isdigit() and int(x) <= 255 for x in parts):
+                raise SystemExit("%s: --key is green, blue or R,G,B (0..255), got %r" % (who, args.key))
+            colour = tuple(int(x) for x in parts)
+        kw = {}
+        if args.key_thresholds is not None:
+            try:
+                kw["lo"], kw["hi"] = (float(x) for x in args.key_thresholds.split(","))
+            except ValueError:
+                raise SystemExit("%s: --key-thresholds is LO,HI with LO < HI, got %r" % (who, args.key_thresholds))
+        try:
+            keys.ChromaKey(colour, **kw)
+        except ValueError as e:
+            raise SystemExit("%s: --key: %s" % (who, e))
+        return lambda band, mask_lo, mask_hi, H, W, rgb: keys.ChromaKey(colour, band=band, mask_lo=mask_lo, mask_hi=mask_hi, **kw)
+    kw = {}
+    if args.plate_thresholds is not None:
+        try:
+            kw["lo"], kw["hi"] = (int(x) for x in args.plate_thresholds.split(","))
+            if not 0 <= kw["lo"] < kw["hi"] <= 255:
+                raise ValueError
+        except ValueError:
+            raise SystemExit("%s: --plate-thresholds is LO,HI with 0 <= LO < HI <= 255, got %r" % (who, args.plate_thresholds))
+    if args.plate_radius is not None:
+        if not 0 <= args.plate_radius <= 3:
+            raise SystemExit("%s: --plate-radius is 0 ... 3, got %d" % (who, args.plate_radius))
+        kw["radius"] = args.plate_radius
+    if not os.path.exists(args.plate):
+        raise SystemExit("%s: --plate %s is not an existing image" % (who, args.plate))
+    path = args.plate
+
+    def make(band, mask_lo, mask_hi, H, W, rgb):
+        import numpy as np
+        from PIL import Image
+        arr = np.asarray(Image.open(path).convert("RGB"))
+        if arr.shape[:2] != (H, W):
+            raise SystemExit("%s: --plate %s is %dx%d, the frames are %dx%d (a plate is given at the frames' resolution)"
+                             % (who, path, arr.shape[1], arr.shape[0], W, H))
+        return keys.PlateKey(np.ascontiguousarray(arr if rgb else arr[..., ::-1]), band=band, mask_lo=mask_lo, mask_hi=mask_hi, **kw)
+    return make
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--data", required=True)
@@ -179,6 +262,7 @@ def main(argv=None):
                     help="--masks: reach of the unknown band into foreground / background in pixels (default: the --trimap dilation)")
     ap.add_argument("--mask-thresholds", default="127,128", metavar="LO,HI",
                     help="--masks: foreground is mask >= HI, background mask <= LO (8-bit scale)")
+    add_key_arguments(ap)
     ap.add_argument("--stabilise", type=float, nargs="?", const=0.5, default=None, metavar="K",
                     help="demo layout: temporal stabilisation of alpha, a flow-compensated recursive filter of strength K in [0,1] "
                          "(default 0.5: a placeholder, not tuned on real footage)")
@@ -263,6 +347,21 @@ def main(argv=None):
         raise SystemExit("eval_cli: --masks frame mattes every frame from its own mask and propagates nothing: there is no trimap "
                          "for --keyframes to place or correct; use --masks key")
 
+    make_key = parse_key_options(args)
+    if make_key is not None:
+        flag = "--key" if args.key is not None else "--plate"
+        if not args.demo:
+            raise SystemExit("eval_cli: %s belongs to the demo routes (the VideoMatting108 flow derives its trimap from the ground "
+                             "truth); add --demo" % flag)
+        for on, other in ((args.masks, "--masks"), (args.keyframes, "--keyframes"), (args.subjects, "--subjects"),
+                          (args.batch is not None and args.batch > 1, "--batch > 1")):
+            if on:
+                raise SystemExit("eval_cli: %s mattes every frame of ONE clip from the trimap of its own key and excludes %s"
+                                 % (flag, other))
+        if roi is not None and (roi == "track" or roi[0] == "track"):
+            raise SystemExit("eval_cli: --roi track follows a propagated trimap; %s propagates nothing, and --roi auto already "
+                             "tracks there" % flag)
+
     if args.subjects_overlap is not None and not args.subjects:
         raise SystemExit("eval_cli: --subjects-overlap belongs to --subjects")
     if args.subjects:
@@ -336,7 +435,7 @@ def main(argv=None):
         #  front -- so they keep batch 1 unless --batch is given explicitly)
         if world > 1 and any(k is not None for k in keys) and not (args.viz or args.sync_io or args.fgr or args.composite
                                                                    or args.keyframes or args.masks or stabilise is not None
-                                                                   or roi is not None or args.subjects):
+                                                                   or roi is not None or args.subjects or make_key is not None):
             def padded(k):
                 lw, uw, lh, uh = pad_amounts(k[0], k[1], 32)
                 return (k[0] + lh + uh) * (k[1] + lw + uw)
@@ -422,7 +521,8 @@ def main(argv=None):
         demo = seq["item"][0] == "demo"
         keyed = demo and (args.keyframes or args.masks == "key")   # frames in schedule order: decoded up front, not prefetched
         data = datasets.load_sequence(seq["item"], max_frames=args.max_frames, decode_frames=not demo or args.sync_io or keyed,
-                                      keyframes=demo and args.keyframes, masks=demo and bool(args.masks))
+                                      keyframes=demo and args.keyframes,
+                                      masks=demo and (bool(args.masks) or make_key is not None))   # (a key needs no trimap/)
         outdir = os.path.join(root_out, "pred", seq["name"])
         os.makedirs(outdir, exist_ok=True)
         vizdir = os.path.join(args.out, "viz", "test", helpers.get_model_name(cfg), "viz", seq["name"])
@@ -501,8 +601,16 @@ def main(argv=None):
                     if not (mk or (data["keyframe_trimaps"] if args.keyframes else data["trimap"] is not None)):
                         raise SystemExit("eval_cli: sequence %s has neither a trimap nor a mask on any frame (%s/%s/trimap|mask/"
                                          "<frame>.png)" % (seq["name"], seq["item"][1], seq["name"]))
-            res = run_video_matte(model, frames, trimap=None if (keyed or per_frame is not None) else data["trimap"], skip=args.skip,
-                                  max_num=args.max_num, masks=per_frame,
+            clip_key = None
+            if make_key is not None and resolution(seq) is not None:
+                # --roi auto reads every frame twice: the decoded list can be, the prefetcher cannot
+                if roi == "auto" and pre is not None:
+                    pre.close()
+                    data = datasets.load_sequence(seq["item"], max_frames=args.max_frames, decode_frames=True, masks=True)
+                    frames, rgb, pre, bgr = data["frames"], False, None, True
+                clip_key = make_key(mask_band, mask_lo, mask_hi, *resolution(seq), rgb)
+            res = run_video_matte(model, frames, trimap=None if (keyed or per_frame is not None or clip_key is not None) else data["trimap"],
+                                  skip=args.skip, max_num=args.max_num, masks=per_frame, key=clip_key,
                                   on_frame=save, device=dev, frames_are_rgb=rgb, keep_on_device=True,
                                   foreground=want_fgr, new_background=new_background(), keyframes=kf,
                                   stabilise=stabilise, **(dict(roi=roi, roi_margin=roi_margin) if roi is not None else {}),
@@ -573,6 +681,8 @@ def main(argv=None):
         summary["masks"] = args.masks
         summary["mask_band"] = list(mask_band) if isinstance(mask_band, tuple) else [dk if mask_band is None else mask_band] * 2
         summary["mask_thresholds"] = [mask_lo, mask_hi]
+    if make_key is not None:
+        summary["key"] = args.key if args.key is not None else "plate"
     if roi is not None:
         summary["roi"], summary["roi_margin"] = (roi if isinstance(roi, str) else list(roi)), roi_margin
         summary["roi_size"] = {seqs[i]["name"]: o["roi_size"] for i, o in summary["outputs"].items() if o.get("roi_size")}

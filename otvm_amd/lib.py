@@ -158,6 +158,17 @@ class RgbToYuv420Params(C.Structure):
                 ("u8_rgb", i32), ("img", vp), ("y", vp), ("u", vp), ("v", vp)]
 
 
+class MaskFromChromaParams(C.Structure):
+    """otvm_mask_from_chroma_params (additive to ABI 21)"""
+    _fields_ = [("frame", vp), ("mask", vp), ("H", i32), ("W", i32), ("u8_rgb", i32), ("kb", i32), ("kr", i32), ("qlo", i32),
+                ("qhi", i32)]
+
+
+class MaskFromPlateParams(C.Structure):
+    """otvm_mask_from_plate_params (additive to ABI 21)"""
+    _fields_ = [("frame", vp), ("plate", vp), ("mask", vp), ("H", i32), ("W", i32), ("radius", i32), ("lo", i32), ("hi", i32)]
+
+
 YUV_420P, YUV_NV12, YUV_422P, YUV_444P, YUV_MONO = 0, 1, 2, 3, 4
 YUV_BT601, YUV_BT709 = 0, 1
 YUV_LIMITED, YUV_FULL = 0, 1
@@ -253,6 +264,8 @@ _PROTOS = {
     "otvm_subjects_resolve": (i32, [C.POINTER(SubjectsResolveParams), vp]),
     "otvm_yuv_to_rgb": (i32, [C.POINTER(YuvToRgbParams), vp]),
     "otvm_rgb_to_yuv420": (i32, [C.POINTER(RgbToYuv420Params), vp]),
+    "otvm_mask_from_chroma": (i32, [C.POINTER(MaskFromChromaParams), vp]),
+    "otvm_mask_from_plate": (i32, [C.POINTER(MaskFromPlateParams), vp]),
     "otvm_gn_stats_b": (i32, [vp, i64, i32, i32, vp, i32, i64, i32, vp]),
     "otvm_gn_table_b": (i32, [vp, i64, i32, vp, vp, vp, vp, i32, i32, i32, vp]),
     "otvm_gn_apply_b": (i32, [C.POINTER(GnApplyParams), vp]),

@@ -226,7 +226,7 @@ def _check_frame(f, t, HW):
 
 @torch.no_grad()
 def run_video_matte_subjects(model, frames, subjects, roi="track", roi_margin=32, overlap="keep", skip=10, max_num=5,
-                             frames_are_rgb=False, foreground=False, keep_on_device=False, on_frame=None, device=None):
+                             frames_are_rgb=False, foreground=False, keep_on_device=False, on_frame=None, device=None, key=None):
     """Matte S subjects of ONE clip in one pass: a full-resolution matte per subject, their union and an owner map.
 
     model      : EvalModel on the GPU, precision f16x3 (the lock-step batch's own limit)
@@ -251,7 +251,11 @@ def run_video_matte_subjects(model, frames, subjects, roi="track", roi_margin=32
     Every window size x S is an engine plan of its own and nothing is evicted here (EvalModel.drop_plans between clips).
     Returns dict(alpha [S,T,H,W], alpha_u8, trimap [S,T,3,H,W], union [T,H,W], union_u8, owner [T,H,W] uint8 (255: nobody's),
     bank_frames, roi = per subject [(y0, x0, h, w)] * T, roi_size, roi_clipped = per subject the frames whose box reaches a window
-    side that is not the frame's[, fgr_u8]).  Checked by definition only, with synthetic weights (the module's docstring)."""
+    side that is not the frame's[, fgr_u8]).  Checked by definition only, with synthetic weights (the module's docstring).
+    ``key`` (run_video_matte's trimap-free matting of keyed footage) is refused: a key makes ONE mask, not one per subject."""
+    if key is not None:
+        raise ValueError("%s: key (trimap-free matting of keyed footage) is a single-clip feature (run_video_matte): a key makes one "
+                         "mask of the frame, not one per subject" % WHO)
     frames = list(frames) if not (hasattr(frames, "shape") or hasattr(frames, "__getitem__")) else frames
     spec, margin, (H, W) = _refuse(model, frames, subjects, roi, roi_margin, overlap)
     T, S = len(frames), len(subjects)

@@ -9,7 +9,7 @@ import contextlib
 import numpy as np
 import torch
 
-from . import guided, temporal
+from . import guided, keys, temporal
 from . import roi as _roi
 from .alpha_model import background_colour
 from .masks import Mask, as_mask
@@ -143,8 +143,13 @@ class _ClipPlan:
     The model is only asked for the band of a Mask that names none."""
 
     def __init__(self, model, frames, trimap, alphas, keyframes, mask, masks, backgrounds, work_scale, work_radius, work_eps, skip,
-                 max_num, roi=None, roi_margin=32):
+                 max_num, roi=None, roi_margin=32, key=None, frames_are_rgb=False):
         self.roi, self.region = None, None                # the checked (window or "auto", margin); run_video_matte's _RegionOfInterest
+        self.key, self.frames, self.rereadable = None, None, False                # ``key``: the key and the source the pre-pass of roi="auto" reads again
+        if key is not None:
+            masks = self._keyed(key, frames, frames_are_rgb, roi, (("trimap", trimap), ("mask", mask), ("masks", masks),
+                                                                   ("keyframes", keyframes), ("alphas", alphas),
+                                                                   ("backgrounds", backgrounds)))
         if roi is not None:
             # (host only, like everything here: the window itself is placed by upload(), which has the sources on the device)
             self.roi = _RegionOfInterest.refuse(roi, roi_margin, frames, alphas, backgrounds, work_scale, masks)
@@ -215,7 +220,7 @@ class _ClipPlan:
         if T == 0:
             return
         for t, v in (self.sources or {}).items():
-            if isinstance(v, Mask):
+            if isinstance(v, Mask) and v.shape is not None:       # (a key's mask has its frame's size by construction)
                 self.mask_hw[t] = v.shape
                 if not self.per_frame:
                     v.band_for(model)                     # (as above: a missing band is refused before anything is uploaded)
@@ -237,6 +242,38 @@ class _ClipPlan:
         else:
             self.steps = [(i, "frame", i == 0, i == T - 1, None) for i in range(T)]  # alpha flow: eval.py's loop as it is
         self.natural = all(st[0] == j for j, st in enumerate(self.steps))
+
+    def _keyed(self, key, frames, frames_are_rgb, roi, others):
+        """``key``: every refusal that needs no frame, then one keys.KeyedMask per frame -- the ``masks`` the rest of the plan sees."""
+        for name, other in others:
+            if other is not None:
+                raise ValueError("run_video_matte: `key` mattes every frame from the trimap of its own key and excludes `%s`" % name)
+        self.key = keys.check_key(key)
+        if _roi.track_spec(roi, "run_video_matte") is not None:
+            raise ValueError("run_video_matte: roi='track' follows a PROPAGATED trimap; `key` mattes every frame from its own key, "
+                             "and roi='auto' already tracks there")
+        plain = isinstance(frames, (list, tuple, np.ndarray)) or torch.is_tensor(frames)
+        self.rereadable = plain or bool(getattr(frames, "rereadable", False))
+        if isinstance(roi, str) and roi == "auto" and not self.rereadable:
+            raise ValueError("run_video_matte: `key` with roi='auto' reads every frame twice (a pre-pass takes the box of every "
+                             "frame's unknown band), and this source can be read once; give a window roi=(y0, x0, h, w)")
+        if plain and len(frames) > 0:
+            f0 = _as_tensor(frames[0])
+            self.check_keyed_frame(f0)
+        self.frames = frames
+        return [keys.KeyedMask(key, frames_are_rgb) for _ in range(len(frames))]
+
+    def check_keyed_frame(self, f):
+        """(a plain sequence: before anything is uploaded; a streaming source: frame by frame, in the loop)"""
+        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != 3:
+            raise ValueError("run_video_matte: `key` takes uint8 [H,W,3] frames (float frames have no key route), got %s %s"
+                             % (f.dtype, tuple(f.shape)))
+        self.key.check_frames(int(f.shape[0]), int(f.shape[1]))
+
+    def bind(self, i, frame):
+        """``key``: frame ``i`` as it is staged on the device is what its key is taken from (nothing is uploaded for it)"""
+        if self.key is not None:
+            self.sources[i].bind(frame)
 
     def _schedule(self, h, w):
         """The keyframe steps of a clip the model runs at h x w (the large-input rule doubles the effective skip)."""
@@ -276,6 +313,8 @@ class _ClipPlan:
     def _track(self, dev):
         """``masks`` with ``roi``: the pre-pass.  Every mask is converted and the box of its unknown band taken -- T box calls into
         one [T,8] buffer, ONE read-back -- and the region places a window per frame.  No trimap is kept: inputs() converts again."""
+        if self.key is not None:
+            return self._track_keyed(dev)
         if len(set(self.mask_hw.values())) != 1:
             raise ValueError("run_video_matte: roi needs masks of one resolution, got %s" % sorted(set(self.mask_hw.values())))
         (H, W), = set(self.mask_hw.values())
@@ -283,6 +322,28 @@ class _ClipPlan:
         for t in range(self.T):
             _roi.trimap_bbox(self.sources[t].convert(self.model, dev), rows[t])
         self.region.place_tracking(_roi.boxes_of(rows)[0], H, W)
+
+    def _track_keyed(self, dev):
+        """``key`` with ``roi``: the same pre-pass, with one extra upload of each frame -- its key is taken, converted and boxed; T box
+        calls into one [T,8] buffer, ONE read-back.  Nothing is kept: the frame loop stages and keys every frame again.  A window
+        given by the caller is held against every frame's band by the same pre-pass, as ``masks`` holds it, when the source can be
+        read twice; a source that is read once cannot be, and there the window is taken as it is."""
+        if self.region.spec != "auto" and not self.rereadable:
+            return self.region.place_fixed(self.T)
+        rows, HW = torch.empty((self.T, 8), dtype=torch.int32, device=dev), None
+        for t in range(self.T):
+            f = _as_tensor(self.frames[t])
+            self.check_keyed_frame(f)
+            if HW is not None and tuple(f.shape[:2]) != HW:
+                raise ValueError("run_video_matte: roi needs frames of one resolution, got %dx%d and %dx%d" % (HW + tuple(f.shape[:2])))
+            HW = tuple(f.shape[:2])
+            ready = getattr(f, "_otvm_ready", None)
+            if ready is not None:
+                torch.cuda.current_stream(dev).wait_event(ready)
+            self.sources[t].bind(f.to(dev, non_blocking=True))
+            _roi.trimap_bbox(self.sources[t].convert(self.model, dev), rows[t])
+            self.sources[t].bind(None)
+        self.region.place_tracking(_roi.boxes_of(rows)[0], HW[0], HW[1])
 
     def _window(self, plain, dev):
         """``roi`` with sources that serve the whole clip: the region places ONE window from the union of their non-background
@@ -312,6 +373,8 @@ class _ClipPlan:
         """The one refusal of the masks that needs a frame: masks of a keyframe clip are all held against the first frame that
         comes by, those of ``masks`` each against its own."""
         for t in ([i] if self.per_frame else list(self.mask_hw)):
+            if t not in self.mask_hw:
+                continue                                  # (``key``: the frame itself was checked when it was bound)
             hw = self.mask_hw.pop(t)
             if tuple(hw) != tuple(full_hw):
                 raise ValueError("run_video_matte: the mask of frame %d is %dx%d, the frames are %dx%d (masks are given at "
@@ -431,6 +494,7 @@ class _RegionOfInterest:
         self.rows, self.seen = None, []                   # static: [T,8] boxes of the output trimaps, in window coordinates
         self.follows = isinstance(self.spec, tuple) and self.spec[0] == "track"     # place_track's mode
         self.track_size, self.log, self.sources, self.source_rows = None, None, {}, {}
+        self.pending = 0                                  # place_fixed: the frames whose window waits for the first frame's size
 
     @staticmethod
     def refuse(spec, margin, frames, alphas, backgrounds, work_scale, masks=None):
@@ -490,6 +554,12 @@ class _RegionOfInterest:
                                  "%d ... %d, columns %d ... %d)" % (win, t, box[0], box[2], box[1], box[3]))
         self.windows = [win] * len(unknown)
 
+    def place_fixed(self, T):
+        """``key`` with a window given by the caller and a source that is read once: no pre-pass is possible, nothing is known of
+        the frames yet.  The window is held against the first frame's size in stage(); it is NOT held
+        against the frames' unknown bands, which only a read-back could tell: outside it alpha follows the frame's own trimap."""
+        self.tracking, self.pending = True, T
+
     def place_static(self, nonbg, H, W, T):
         """nonbg: {frame: the non-background box of the source given for it}"""
         self.HW = (H, W)
@@ -529,6 +599,9 @@ class _RegionOfInterest:
         if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != 3:
             raise ValueError("run_video_matte: roi takes uint8 [H,W,3] frames (float frames have no region-of-interest "
                              "route), got %s %s" % (f.dtype, tuple(f.shape)))
+        if self.HW is None and self.pending:
+            self.HW = tuple(int(v) for v in f.shape[:2])
+            self.windows = [_roi.check_window(self.spec, self.HW[0], self.HW[1], "run_video_matte: roi")] * self.pending
         if tuple(f.shape[:2]) != self.HW:
             raise ValueError("run_video_matte: frame %d is %dx%d, the trimaps the window was placed in are %dx%d"
                              % ((i,) + tuple(f.shape[:2]) + self.HW))
@@ -536,6 +609,7 @@ class _RegionOfInterest:
         self.full = f.to(dev, non_blocking=True).contiguous()
         if ready is not None:
             torch.cuda.current_stream(dev).wait_event(ready)
+        self.plan.bind(i, self.full)
         if self.follows:
             return self._stage_track(i, dev)
         win = self.windows[i]
@@ -706,7 +780,7 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                     frames_are_rgb=False, on_frame=None, device=None, keep_on_device=False, gt_alpha_u8=None,
                     gt_mask_u8=None, gt_mask=None, gt_image_metrics=False, gt_flow_metrics=False, foreground=False,
                     new_background=None, keyframes=None, work_scale=None, work_radius=2, work_eps=1e-4, on_foreground=None,
-                    mask=None, masks=None, stabilise=None, roi=None, roi_margin=32):
+                    mask=None, masks=None, stabilise=None, roi=None, roi_margin=32, key=None):
     """Matte one sequence.
 
     model       : EvalModel (optionally wrapped in nn.DataParallel), on the GPU
@@ -802,6 +876,24 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                   the origins and the output boxes once after the last.  The window LAGS ONE FRAME: a subject that moves more than
                   ``hold`` pixels a frame, or outgrows the size, is cut -- roi_clipped lists those frames.  Outside the window
                   everything is background.  Checked by definition only, as above; refused with ``masks`` ("auto" tracks there).
+    key         : a keys.ChromaKey (footage shot against a green / blue screen) or a keys.PlateKey (a locked-off shot with a clean
+                  plate of the empty set): TRIMAP-FREE matting.  The mask of every frame is made on the device from the frame itself,
+                  as it is already staged there (otvm_mask_from_chroma / otvm_mask_from_plate: no second upload, nothing read back
+                  in the frame loop), made into a trimap as ``masks`` does, and the frame is matted from it: the ``masks`` route
+                  unchanged -- each step a clip of one frame, natural order, bank_frames [] for every frame -- so ``frames`` may be
+                  a source that is read once (a Y4MFrames on a pipe).  on_frame, the metrics, foreground / new_background /
+                  on_foreground, work_scale (key and band at H x W, the trimap reduced as any other), stabilise and roi (a window,
+                  or "auto") work as with ``masks``; roi="auto" needs the pre-pass over all frames (one extra upload of each, one
+                  read-back of T boxes) and is refused for a source that cannot be read twice (a plain sequence can; any other
+                  source says so with ``rereadable = True``); a window given by the caller is held against every frame's unknown
+                  band by the same pre-pass and refused when one does not fit, as with ``masks`` -- except for a source that is read
+                  once, where no pre-pass is possible: there it is taken as it is, held against the frames' size only (outside it
+                  alpha follows the frame's own trimap; whether the band fits is then the caller's knowledge).  Exclusive with trimap, mask, masks, keyframes, alphas and
+                  backgrounds; refused with roi="track", for float frames and for a plate of another size than the frames; not
+                  available in run_video_matte_batch and run_video_matte_subjects.  To key only the first frame and propagate:
+                  mask=Mask(keys.key_mask(f0, key).cpu()).  The keys are CHECKED BY DEFINITION ONLY (bit for bit against their
+                  restatement) and every default of theirs is a PLACEHOLDER nobody tuned on real footage; with no trained
+                  checkpoint here nothing is claimed about matting quality.
     roi_margin  : pixels kept round the box on every side by roi="auto" / "track", and twice the pixels a tracked box keeps from a
                   window side before the window moves (default 32: a PLACEHOLDER nobody tuned on real footage)
     Returns dict(alpha=[T,H,W] float32, alpha_u8=[T,H,W] uint8 (truncated, eval.py:209), trimap=[T,3,H,W],
@@ -812,7 +904,7 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
     T = len(frames)
     dev = device or next(model.parameters()).device
     plan = _ClipPlan(model, frames, trimap, alphas, keyframes, mask, masks, backgrounds, work_scale, work_radius, work_eps, skip,
-                     max_num, roi, roi_margin)
+                     max_num, roi, roi_margin, key, frames_are_rgb)
     stab = temporal.options_of(stabilise)
     if stab is not None:
         _Stabilisation.refuse(plan, frames, backgrounds)
@@ -833,6 +925,8 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
             b = _as_tensor(backgrounds[i]) if backgrounds is not None else None
             if stab is not None:
                 stab.check_frame(f)
+            if plan.key is not None:
+                plan.check_keyed_frame(f)
             fg, bg, H, W, rgb_applies, ready, ready_b = (work.stage(f, dev) if work is not None else
                                                          region.stage(f, i, dev) if region is not None else
                                                          _stage_frame(f, b, dev, frames_are_rgb))
@@ -850,7 +944,10 @@ def run_video_matte(model, frames, trimap=None, alphas=None, backgrounds=None, s
                 else:
                     torch.cuda.current_stream(dev).wait_event(ready)
             plan.check_masks(i, work.full.shape[:2] if work is not None else region.HW if region is not None else (H, W))
+            if plan.key is not None and region is None:
+                plan.bind(i, fg if work is None else work.full)   # (roi: bound by region.stage, which converts there)
             a, tri_gt, more = plan.inputs(i, kind, first_frame, H, W, dev)
+            plan.bind(i, None)
             if i == plan.k0 - 1:
                 core.drop_non_anchors()                           # the backward sweep starts from the keyframes alone
             memorize, max_memory_num, large = memory_schedule(i, H, W, skip, max_num)
@@ -915,7 +1012,7 @@ def _metrics_add(metrics, u8, i, gt_alpha_u8, gt_mask_u8, gt_mask, dev):
 def run_video_matte_batch(model, clips, trimaps=None, alphas=None, backgrounds=None, skip=10, max_num=5, frames_are_rgb=False,
                           device=None, keep_on_device=False, on_frame=None, gt_alpha_u8=None, gt_mask=None,
                           gt_image_metrics=False, gt_flow_metrics=False, foreground=False, new_background=None, keyframes=None,
-                          work_scale=None, mask=None, masks=None, roi=None):
+                          work_scale=None, mask=None, masks=None, roi=None, key=None):
     """Matte B sequences of one resolution in LOCK-STEP (round 3): frame i of every clip goes through the network in one
     batched step (EvalModel.forward_batch: one launch per layer over the B images, per-sequence memory banks).
     clips: list of B frame arrays ([T_b,H,W,3] uint8 / float, BGR unless frames_are_rgb); trimaps: list of B first-frame
@@ -940,6 +1037,9 @@ def run_video_matte_batch(model, clips, trimaps=None, alphas=None, backgrounds=N
                          "(run_video_matte); lock-step batches run at the frames' resolution")
     if mask is not None or masks is not None or (trimaps is not None and any(isinstance(t, Mask) for t in trimaps)):
         raise ValueError("run_video_matte_batch: trimaps from masks (mask / masks / a Mask) are a single-clip feature "
+                         "(run_video_matte); lock-step batches take trimaps")
+    if key is not None:
+        raise ValueError("run_video_matte_batch: key (trimap-free matting of keyed footage) is a single-clip feature "
                          "(run_video_matte); lock-step batches take trimaps")
     if roi is not None:
         raise ValueError("run_video_matte_batch: roi (region-of-interest matting) is a single-clip feature (run_video_matte); the "

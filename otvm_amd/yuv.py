@@ -355,6 +355,11 @@ class Y4MFrames:
     def __len__(self):
         return self.reader.T
 
+    @property
+    def rereadable(self):
+        """Whether a frame can be asked for a second time (a seekable file; not a pipe): what a pre-pass over the clip needs"""
+        return self.reader.seekable
+
     def _load(self, i):
         host = torch.empty(self.reader.nbytes, dtype=torch.uint8, pin_memory=True)
         self.reader.read_into(i, host.numpy())             # straight into the pinned staging buffer
